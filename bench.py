@@ -6,7 +6,16 @@ One "step" = one full forward transform (log_h = 24, log_rate = 0) of a device-r
 synthetic GF(2^128) vector (numpy PCG64, seed 0xdeadbeef + 24 + rank) into a separate device
 output buffer. The oracle (test infrastructure) is used only by the cpu_baseline leg.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-h 24] [--no-cpu] [--no-c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-h 24] [--dump-outputs DIR]
+                  [--full [--no-cpu] [--no-c5] [--no-configs]]
+
+A plain run sets up, warms up, times the K transforms and prints the headline line (metric, value,
+ms_per_step, ...). --dump-outputs DIR then writes the last timed transform's output (rank 0) as
+DIR/additive_ntt_out.npy: float64 (exact for u32 limbs), shape (rows, 4), all rows up to 2^20 points and
+a fixed seeded sample of 2^20 rows (ascending) above that. The inputs are seeded, so two builds can
+be compared output for output. Everything else is measured only with --full: the per-pass timings
+and rooflines, the limb-0 MD5 check against the reference table, the c5 and configs legs listed
+below, apply_e2e and the CPU baseline.
 
 --gpus N > 1 without a torch.distributed environment re-launches this script as a child
 `python -m torch.distributed.run --nproc-per-node N` (before anything touches the GPU) and exits
@@ -48,9 +57,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log-h", type=int, default=24)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-c5", action="store_true", help="skip the config-5 legs")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs 2-4 leg (world 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed transform's output to DIR/additive_ntt_out.npy (float64, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: per-pass timings and rooflines, the output "
+                         "MD5 check, the c5 and configs legs, apply_e2e and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-c5", action="store_true", help="with --full: skip the config-5 legs")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="with --full: skip the configs 2-4 leg (world 1 only)")
     ap.add_argument("--c5-log-n", type=int, default=20)
     ap.add_argument("--c5-batch", type=int, default=256)
     ap.add_argument("--c5-steps", type=int, default=3)
@@ -65,7 +80,25 @@ def parse():
                     help="CPU rehearsal of the launch path: the --gpus relaunch, process-group setup (gloo), "
                          "barriers, max-over-ranks timing, batch slicing and the sharded message exchange, "
                          "with no GPU work; prints one JSON line")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_ROWS = 1 << 20  # 2^20 rows x 4 limbs x 8 B = 32 MB of float64
+SETTLE_SECONDS = 0.3  # untimed transforms before a plain run's timed steps (see main)
+
+
+def dump_outputs(path, d_out, n, torch, np):
+    """--dump-outputs: the timed transform's output (n GF(2^128) elements as u32 limbs) as float64,
+    whole up to DUMP_ROWS elements, else the rows of a fixed seeded sample (ascending)."""
+    rows = d_out.view(-1, 4)
+    if n > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(0xD0A7).choice(n, size=DUMP_ROWS, replace=False))
+        rows = rows[torch.from_numpy(idx).to(d_out.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "additive_ntt_out.npy"), rows.cpu().numpy().view(np.uint32).astype(np.float64))
 
 
 def relaunch_if_needed(a):
@@ -427,29 +460,70 @@ def main():
         ntt.forward_device(d_in, d_out, stream=stream)
     torch.cuda.synchronize(dev)
 
-    # per-pass durations inside the back-to-back transform loop: hipEvents recorded between the
-    # pass launches of consecutive transforms (no host synchronisation between launches), averaged
-    # per pass; profiles/r02 holds the rocprofv3 kernel trace of the same loop for comparison
-    ntt.set_event_timing(True)
-    for _ in range(max(5, min(a.steps, 20))):
-        ntt.forward_device(d_in, d_out, stream=stream)
-    torch.cuda.synchronize(dev)
-    pass_ms_inloop = ntt.event_timing()
-    ntt.set_event_timing(False)
-    # steady-state duration per launch of each pass: the pass launched back to back between two
-    # events only (bn_antt_time_passes), so no event sits between the timed launches; d_out is
-    # scratch here and is overwritten by the timed loop below
-    pass_ms = ntt.time_passes(d_in, d_out, reps=max(10, min(a.steps, 40)), stream=stream)
-    torch.cuda.synchronize(dev)
+    if a.full:
+        # per-pass durations inside the back-to-back transform loop: hipEvents recorded between the
+        # pass launches of consecutive transforms (no host synchronisation between launches), averaged
+        # per pass; profiles/r02 holds the rocprofv3 kernel trace of the same loop for comparison
+        ntt.set_event_timing(True)
+        for _ in range(max(5, min(a.steps, 20))):
+            ntt.forward_device(d_in, d_out, stream=stream)
+        torch.cuda.synchronize(dev)
+        pass_ms_inloop = ntt.event_timing()
+        ntt.set_event_timing(False)
+        # steady-state duration per launch of each pass: the pass launched back to back between two
+        # events only (bn_antt_time_passes), so no event sits between the timed launches; d_out is
+        # scratch here and is overwritten by the timed loop below
+        pass_ms = ntt.time_passes(d_in, d_out, reps=max(10, min(a.steps, 40)), stream=stream)
+        torch.cuda.synchronize(dev)
+    else:
+        # the GPU's clocks reach their steady state only after tens of milliseconds of load: a few
+        # warm-up transforms (0.7 ms each) do not get there, the per-pass loops above do. A plain
+        # run keeps the device busy with untimed transforms for SETTLE_SECONDS instead, so that
+        # ms_per_step is the same steady-state figure with and without --full
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < SETTLE_SECONDS:
+            for _ in range(10):
+                ntt.forward_device(d_in, d_out, stream=stream)
+            torch.cuda.synchronize(dev)
 
     dt = timed(lambda: ntt.forward_device(d_in, d_out, stream=stream), a.steps)
     ms_step = dt / a.steps * 1e3
-    out_check = limb0_check(d_out, log_h)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, d_out, n, torch, np)
     elems_per_s = world * n / (dt / a.steps)
     alg_bytes = 2 * 16 * n  # read input once + write output once
     transform_gbps = alg_bytes / (ms_step * 1e-3) / 1e9
 
     res = None
+    if rank == 0:
+        res = {
+            "metric": "GF(2^128) additive-NTT elements/sec (2^%d pts)" % log_h,
+            "value": elems_per_s,
+            "unit": "elements/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": ms_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "gf2_128 (u32 limbs, bitwise)",
+            "data": "synthetic: limb 0 = std::mt19937(0xdeadbeef + log_h) (the reference test stream), limbs 1-3 "
+                    "numpy PCG64",
+            "config": {"workload": "additive NTT over GF(2^128), log_h=%d, log_rate=0, one transform per GPU"
+                                   % log_h, "log_h": log_h, "log_rate": 0, "field": "GF(2^128)",
+                       "kernel_variant": ntt.variant(), "parallelism": "independent transform per rank"},
+            "hbm_gbps_transform": transform_gbps,
+        }
+    if not a.full:
+        if rank == 0:
+            json_out.write(json.dumps(res) + "\n")
+            json_out.flush()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    out_check = limb0_check(d_out, log_h)
     if rank == 0:
         # dominant kernel = the pass with the largest mean duration; every pass reads and writes
         # the whole vector once, so its algorithmic bytes are the same 32 B/element
@@ -470,28 +544,11 @@ def main():
                     # microbench4.hip), not the nominal 0.5
                     "bitop3_ceiling_frac": rate / BITOP3_CEILING,
                     "source": PMC_FILE + " (library SHA-256 checked)"}
-        res = {
-            "metric": "GF(2^128) additive-NTT elements/sec (2^%d pts)" % log_h,
-            "value": elems_per_s,
-            "unit": "elements/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": ms_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "gf2_128 (u32 limbs, bitwise)",
-            "data": "synthetic: limb 0 = std::mt19937(0xdeadbeef + log_h) (the reference test stream), limbs 1-3 "
-                    "numpy PCG64",
+        # kept in the driver's parsed record (the top-level output_check is not)
+        res["config"]["output_check"] = ("limb-0 MD5 of the timed output %s additive_ntt_hashes[0][%d] (%s)"
+                                         % ("==" if out_check["match"] else "!=", log_h, out_check["limb0_md5"]))
+        res.update({
             "output_check": out_check,
-            "config": {"workload": "additive NTT over GF(2^128), log_h=%d, log_rate=0, one transform per GPU"
-                                   % log_h, "log_h": log_h, "log_rate": 0, "field": "GF(2^128)",
-                       "kernel_variant": ntt.variant(), "parallelism": "independent transform per rank",
-                       # kept in the driver's parsed record (the top-level output_check is not)
-                       "output_check": "limb-0 MD5 of the timed output %s additive_ntt_hashes[0][%d] (%s)"
-                                       % ("==" if out_check["match"] else "!=", log_h, out_check["limb0_md5"])},
-            "hbm_gbps_transform": transform_gbps,
             "roofline": {
                 # the roofline the metric is priced against (the north star's HBM roofline); what
                 # actually binds the kernel is binding_resource below (VALU issue), see valu_transform
@@ -517,7 +574,7 @@ def main():
             },
             "valu": valu,
             "valu_transform": valu_transform(ntt, len(pass_ms), ms_step, alg_bytes),
-        }
+        })
     del d_in, d_out
 
     # ---------------- config 5: 256 x 2^20 batched NTT, sharded by transform

@@ -1,6 +1,6 @@
 """Host-side checks of the measurement tools (no GPU): tools/trace_passes.py splits a rocprofv3
-kernel trace of bench.py into its launch phases (warm-up, in-loop events, isolated pass loops,
-timed transforms) exactly as bench.py orders them."""
+kernel trace of bench.py --full into its launch phases (warm-up, in-loop events, isolated pass loops,
+timed transforms) exactly as bench.py --full orders them."""
 import csv
 import json
 import os

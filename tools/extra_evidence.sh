@@ -13,7 +13,7 @@ bash tools/prof_sumcheck.sh > /dev/null || exit 1
 cp gpurun_out/prof_sc/run_kernel_stats.csv "$P/sumcheck_c4_d3_kernel_stats.csv"
 python3 tools/sc_round_gaps.py gpurun_out/prof_sc/run_kernel_trace.csv 24 > "$P/sumcheck_c4_d3_rounds.txt" || exit 1
 rm -rf gpurun_out/scpmc && mkdir -p gpurun_out/scpmc
-PMC_GROUPS=sq,stall PMC_TAG=sc_ PMC_SCRIPT=tools/bench_configs.py PMC_ARGS="--only c4 --sc-d 3" bash tools/pmc.sh || exit 1
+OUT_DIR="$(dirname "$P")" PMC_GROUPS=sq,stall PMC_TAG=sc_ PMC_SCRIPT=tools/bench_configs.py PMC_ARGS="--only c4 --sc-d 3" bash tools/pmc.sh || exit 1
 mv gpurun_out/pmc_sc_* gpurun_out/scpmc/
 python3 tools/pmc_summary.py gpurun_out/scpmc > "$P/pmc_sumcheck_c4_d3.txt" || exit 1
 c3() {  # tag, env...

@@ -16,8 +16,8 @@ trace() {  # tag, library
 }
 trace fused "$R/binius-ntt_amd/lib-fu/libbinius_ntt_amd.so" && trace separate "$R/binius-ntt_amd/lib/libbinius_ntt_amd.so" || exit 1
 export BINIUS_NTT_AMD_LIB="$R/binius-ntt_amd/lib-fu/libbinius_ntt_amd.so"
-PMC_GROUPS=fetch,write,stall PMC_TAG=fu_ PMC_SCRIPT=tools/bench_configs.py PMC_ARGS="--only c4 --sc-d 3" bash tools/pmc.sh || exit 1
+OUT_DIR="$R/$(dirname $O)" PMC_GROUPS=fetch,write,stall PMC_TAG=fu_ PMC_SCRIPT=tools/bench_configs.py PMC_ARGS="--only c4 --sc-d 3" bash tools/pmc.sh || exit 1
 unset BINIUS_NTT_AMD_LIB
-PMC_GROUPS=fetch,write,stall PMC_TAG=sep_ PMC_SCRIPT=tools/bench_configs.py PMC_ARGS="--only c4 --sc-d 3" bash tools/pmc.sh || exit 1
+OUT_DIR="$R/$(dirname $O)" PMC_GROUPS=fetch,write,stall PMC_TAG=sep_ PMC_SCRIPT=tools/bench_configs.py PMC_ARGS="--only c4 --sc-d 3" bash tools/pmc.sh || exit 1
 mkdir -p $O/pmc_fu $O/pmc_sep && mv gpurun_out/pmc_fu_* $O/pmc_fu/ && mv gpurun_out/pmc_sep_* $O/pmc_sep/
 python3 tools/pmc_summary.py $O/pmc_fu > $O/pmc_fused.txt && python3 tools/pmc_summary.py $O/pmc_sep > $O/pmc_separate.txt && echo fused_prof done

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-pass mean durations of the headline NTT's launches from a rocprofv3 kernel trace of
-`bench.py --no-cpu --no-c5 --no-configs --steps K --warmup W` (tools/headline_prof.sh).
+`bench.py --full --no-cpu --no-c5 --no-configs --steps K --warmup W` (tools/round_profile.sh).
 
-bench.py launches every pass kernel in this order: W warm-up transforms, max(5, min(K, 20))
+bench.py --full launches every pass kernel in this order: W warm-up transforms, max(5, min(K, 20))
 transforms with events between the passes (pass_ms_inloop), then each pass 1 + max(10, min(K, 40))
 times back to back (bn_antt_time_passes, pass_ms), then the K timed transforms, then apply_e2e.
 This prints the mean duration of each phase's launches per pass kernel, so the bench's
