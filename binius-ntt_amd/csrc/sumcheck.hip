@@ -125,10 +125,6 @@ struct ScArgs {
 	uint32_t seq;       // this launch's sequence number
 	int post;           // 1: the last workgroup posts the points (small grids), 0: sc_post does
 	uint32_t kcol[kMaxD + 1][4];  // GF(2^4) products k * 2^a (interpolation point k)
-#ifdef BN_SC_FUSED
-	int fm_p;                     // sc_fold_msgs: pairs per work-group P
-	uint32_t fm_magic;            // ... ceil(2^32 / (2 P)): item / (2 P) = umulhi(item, fm_magic) for items < 2^16
-#endif
 	int dbg;  // development build (BN_DEV) only: BN_SC_DBG bit 0 = synthetic operands instead of
 	          // column loads, bit 1 = no products, bit 2 = no k-multiples, bit 3 = no parity
 	          // reduction (wrong results; for timing experiments)
@@ -174,12 +170,34 @@ __device__ __forceinline__ void load_pair(const ScArgs& A, int j, size_t p, int 
 	}
 }
 
-// Reduce the accumulator copies and post the points + sequence word to host-mapped memory.
-__device__ __forceinline__ void post_points(const ScArgs& A, int t) {
+// f_j at point k from its pair: lo <- lo + k (lo + hi) (hi is scratch); kcol[k] as ScArgs::kcol
+__device__ __forceinline__ void point_at(const ScArgs& A, const uint32_t (*kcol)[4], int k, uint32_t* lo, uint32_t* hi) {
+	if (k == 0) {
+	} else if (k == 1) {
+#pragma unroll
+		for (int i = 0; i < 32; i++) lo[i] = hi[i];
+	} else {
+#pragma unroll
+		for (int i = 0; i < 32; i++) hi[i] ^= lo[i];
+#ifdef BN_DEV
+		if (!(A.dbg & 4))
+#endif
+		{
+			if (A.kmax <= 3)  // d <= 3: every k here is 2 or 3 (launch-uniform branch)
+				mul_23(0u - (uint32_t)(k & 1), hi);
+			else
+				mul_small(kcol[k], hi, hi);
+		}
+#pragma unroll
+		for (int i = 0; i < 32; i++) lo[i] ^= hi[i];
+	}
+}
+
+// Post the round: thread t < 4 (kmax + 1) holds point word v. The words go to host-mapped memory
+// (and the sink, with its flag word), then, once every thread's stores are fenced, the sequence
+// word the host polls. Every thread of the workgroup calls this.
+__device__ __forceinline__ void post_words(const ScArgs& A, int t, uint32_t v) {
 	if (t < 4 * (A.kmax + 1)) {
-		uint32_t v = 0;
-		for (int c = 0; c < kAccCopies; c++)
-			v ^= __hip_atomic_load(A.acc + c * kAccStride + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		A.res[t] = v;
 		if (A.sink) A.sink[t] = v;
 	}
@@ -187,6 +205,15 @@ __device__ __forceinline__ void post_points(const ScArgs& A, int t) {
 	__threadfence_system();
 	__syncthreads();
 	if (t == 0) __hip_atomic_store(A.res + kResSeq, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Reduce the accumulator copies and post the points + sequence word to host-mapped memory.
+__device__ __forceinline__ void post_points(const ScArgs& A, int t) {
+	uint32_t v = 0;
+	if (t < 4 * (A.kmax + 1))
+		for (int c = 0; c < kAccCopies; c++)
+			v ^= __hip_atomic_load(A.acc + c * kAccStride + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	post_words(A, t, v);
 }
 
 // Timing-experiment builds only (make BUILD=build-x LIBDIR=lib-x EXTRA=-DBN_SC_SKIP_MID): the
@@ -218,167 +245,34 @@ __device__ __forceinline__ void grp_mul(const Slot& S, const uint32_t* B, int l,
 		wide_mul<B_SHARED>(S, B, l);
 }
 
-// One (pair, point k) per group, k fastest: the kmax+1 groups of a pair run side by side, so the
-// pair's columns are read from HBM once and hit in cache for the other points.
-template <int MODE, int G>
-__global__ __launch_bounds__(kScThreads, kScMinWG) void sc_messages(ScArgs A) {
-	extern __shared__ uint32_t lds[];
-	const int l = threadIdx.x % G, qw = threadIdx.x / G;
-	const Slot S{lds + qw * Grp<G>::kSlotWords};
-	uint32_t* accL = lds + Grp<G>::kSlotsWords + 128;  // (kMaxD + 1) x 4 words
-	if (threadIdx.x < 4 * (kMaxD + 1)) accL[threadIdx.x] = 0;
-	// rounds alternate between two accumulator sets; the other set was last read back by the
-	// previous round's copy (ordered before this launch), so no memset is queued per round
-	if (blockIdx.x == 0)
-		for (int i = threadIdx.x; i < kAccSet; i += kScThreads) A.clr[i] = 0;
-	__syncthreads();
-	const int npts = A.kmax + 1 - A.skip1;
-	const size_t item = (size_t)blockIdx.x * Grp<G>::kGroups + qw;
-	const size_t p = item / npts;
-	const int ki = (int)(item % npts);
-	const int k = (A.skip1 && ki >= 1) ? ki + 1 : ki;
-	if (p < A.n_pairs) {
-		uint32_t emask = 0;
-		for (int j = 0; j < A.d; j++) {
-			// f_j at point k: lo + k (lo + hi), written into the A (j == 0) or B operand
-			if (l < 4) {
-			uint32_t lo[32], hi[32];
-			load_pair<MODE>(A, j, p, l, lo, hi, emask);
-			if (k == 0) {
-			} else if (k == 1) {
-#pragma unroll
-				for (int i = 0; i < 32; i++) lo[i] = hi[i];
-			} else {
-#pragma unroll
-				for (int i = 0; i < 32; i++) hi[i] ^= lo[i];
-#ifdef BN_DEV
-				if (!(A.dbg & 4))
-#endif
-				{
-					if (A.kmax <= 3)  // d <= 3: every k here is 2 or 3 (launch-uniform branch)
-						mul_23(0u - (uint32_t)(k & 1), hi);
-					else
-						mul_small(A.kcol[k], hi, hi);
-				}
-#pragma unroll
-				for (int i = 0; i < 32; i++) lo[i] ^= hi[i];
-			}
-			sst(S, (j == 0 ? 0 : 4) + l, lo);
-			}
-#ifdef BN_DEV
-			if (A.dbg & 2) continue;
-#endif
-			if (j > 0) grp_mul<G, false>(S, nullptr, l, kSkipMid);
-		}
-		wsync();
-		if (l < 4) {
-		uint32_t t[32];
-		sld(t, S, l);
-#ifdef BN_DEV
-		const uint32_t acc = (A.dbg & 8) ? t[0] ^ t[31] : parity_word(t, emask);
-#else
-		const uint32_t acc = parity_word(t, emask);
-#endif
-		if (acc) atomicXor(accL + 4 * k + l, acc);  // LDS atomic
-		}
-	}
-	__syncthreads();
-	if (!A.post) {
-		if (threadIdx.x < 4 * (A.kmax + 1) && accL[threadIdx.x])
-			atomicXor(A.acc + (blockIdx.x % kAccCopies) * kAccStride + threadIdx.x, accL[threadIdx.x]);
-		return;  // sc_post follows
-	}
-	if (gridDim.x == 1) {  // a single workgroup posts its own sums
-		if (threadIdx.x < 4 * (A.kmax + 1)) {
-			A.res[threadIdx.x] = accL[threadIdx.x];
-			if (A.sink) A.sink[threadIdx.x] = accL[threadIdx.x];
-		}
-		if (A.sink && threadIdx.x == 0) A.sink[kResSeq] = (uint32_t)A.skip1 | (A.mode == 2 ? 2u : 0u);
-		__threadfence_system();
-		__syncthreads();
-		if (threadIdx.x == 0) __hip_atomic_store(A.res + kResSeq, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-		return;
-	}
-	// small grids (<= kAccCopies workgroups): workgroup b stores its sums into copy b with plain
-	// stores, the last one to finish XORs the gridDim.x copies and posts the points itself
-	const int nw = 4 * (A.kmax + 1);
-	if (threadIdx.x < nw) A.acc[blockIdx.x * kAccStride + threadIdx.x] = accL[threadIdx.x];
-	uint32_t* last = accL + 4 * (kMaxD + 1);  // (a static __shared__ word cost a workgroup per CU)
-	__syncthreads();
-	if (threadIdx.x == 0)
-		// acq_rel: release orders this workgroup's stores before its count, acquire makes every other
-		// workgroup's stores visible to the last one
-		*last = __hip_atomic_fetch_add(A.acc + kAccCount, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-	__syncthreads();
-	if (!*last) return;
-	__threadfence();
-	uint32_t* red = last + 1;  // 4 (kMaxD + 1) words
-	if (threadIdx.x < nw) red[threadIdx.x] = 0;
-	__syncthreads();
-	// every (copy, word) by one thread, XOR-reduced in LDS
-	for (int i = threadIdx.x; i < (int)gridDim.x * nw; i += kScThreads) {
-		const int b = i / nw, w = i - b * nw;
-		const uint32_t v = __hip_atomic_load(A.acc + b * kAccStride + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (v) atomicXor(red + w, v);
-	}
-	__syncthreads();
-	if (threadIdx.x < nw) {
-		A.res[threadIdx.x] = red[threadIdx.x];
-		if (A.sink) A.sink[threadIdx.x] = red[threadIdx.x];
-	}
-	if (A.sink && threadIdx.x == 0) A.sink[kResSeq] = (uint32_t)A.skip1 | (A.mode == 2 ? 2u : 0u);
-	__threadfence_system();
-	__syncthreads();
-	if (threadIdx.x == 0) __hip_atomic_store(A.res + kResSeq, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-#ifdef BN_SC_FUSED
-// sc_messages's body as device functions for the fused experiment kernel (sc_fold_msgs). The
-// product kernel above keeps its own copy: the product build is round 5's code.
-// the work-group's point sums in LDS (after the product slots); the accumulator set of the next
-// round is cleared by workgroup 0 (rounds alternate between two sets; the other set was last read
-// back by the previous round's post, ordered before this launch, so no memset is queued per round)
+// The workgroup's point sums in LDS, after the product slots and the fold's challenge rows
+// ((kMaxD + 1) x 4 words, then the last-workgroup flag and reduction: lds_bytes). Rounds alternate
+// between two accumulator sets; the other set was last read back by the previous round's post
+// (ordered before this launch), so workgroup 0 clears it here and no memset is queued per round.
+// The caller's barrier follows.
 template <int G>
 __device__ __forceinline__ uint32_t* messages_init(const ScArgs& A, uint32_t* lds) {
-	uint32_t* accL = lds + Grp<G>::kSlotsWords + 128;  // (kMaxD + 1) x 4 words
+	uint32_t* accL = lds + Grp<G>::kSlotsWords + 128;
 	if (threadIdx.x < 4 * (kMaxD + 1)) accL[threadIdx.x] = 0;
 	if (blockIdx.x == 0)
 		for (int i = threadIdx.x; i < kAccSet; i += kScThreads) A.clr[i] = 0;
 	return accL;
 }
 
-// point k of pair p on this group (when `valid`), then the work-group's reduction and posting
+// Point k of pair p on this lane group (when `valid`), then the workgroup's reduction and posting.
 template <int MODE, int G>
 __device__ __forceinline__ void messages_run(const ScArgs& A, uint32_t* lds, uint32_t* accL, size_t p, int k, bool valid) {
-	const int l = threadIdx.x % G, qw = threadIdx.x / G;
+	const int t = threadIdx.x, l = t % G, qw = t / G;
 	const Slot S{lds + qw * Grp<G>::kSlotWords};
 	if (valid) {
 		uint32_t emask = 0;
 		for (int j = 0; j < A.d; j++) {
-			// f_j at point k: lo + k (lo + hi), written into the A (j == 0) or B operand
+			// f_j at point k, written into the A (j == 0) or B operand
 			if (l < 4) {
-			uint32_t lo[32], hi[32];
-			load_pair<MODE>(A, j, p, l, lo, hi, emask);
-			if (k == 0) {
-			} else if (k == 1) {
-#pragma unroll
-				for (int i = 0; i < 32; i++) lo[i] = hi[i];
-			} else {
-#pragma unroll
-				for (int i = 0; i < 32; i++) hi[i] ^= lo[i];
-#ifdef BN_DEV
-				if (!(A.dbg & 4))
-#endif
-				{
-					if (A.kmax <= 3)  // d <= 3: every k here is 2 or 3 (launch-uniform branch)
-						mul_23(0u - (uint32_t)(k & 1), hi);
-					else
-						mul_small(A.kcol[k], hi, hi);
-				}
-#pragma unroll
-				for (int i = 0; i < 32; i++) lo[i] ^= hi[i];
-			}
-			sst(S, (j == 0 ? 0 : 4) + l, lo);
+				uint32_t lo[32], hi[32];
+				load_pair<MODE>(A, j, p, l, lo, hi, emask);
+				point_at(A, A.kcol, k, lo, hi);
+				sst(S, (j == 0 ? 0 : 4) + l, lo);
 			}
 #ifdef BN_DEV
 			if (A.dbg & 2) continue;
@@ -387,40 +281,32 @@ __device__ __forceinline__ void messages_run(const ScArgs& A, uint32_t* lds, uin
 		}
 		wsync();
 		if (l < 4) {
-		uint32_t t[32];
-		sld(t, S, l);
+			uint32_t w[32];
+			sld(w, S, l);
 #ifdef BN_DEV
-		const uint32_t acc = (A.dbg & 8) ? t[0] ^ t[31] : parity_word(t, emask);
+			const uint32_t acc = (A.dbg & 8) ? w[0] ^ w[31] : parity_word(w, emask);
 #else
-		const uint32_t acc = parity_word(t, emask);
+			const uint32_t acc = parity_word(w, emask);
 #endif
-		if (acc) atomicXor(accL + 4 * k + l, acc);  // LDS atomic
+			if (acc) atomicXor(accL + 4 * k + l, acc);  // LDS atomic
 		}
 	}
 	__syncthreads();
+	const int nw = 4 * (A.kmax + 1);
 	if (!A.post) {
-		if (threadIdx.x < 4 * (A.kmax + 1) && accL[threadIdx.x])
-			atomicXor(A.acc + (blockIdx.x % kAccCopies) * kAccStride + threadIdx.x, accL[threadIdx.x]);
+		if (t < nw && accL[t]) atomicXor(A.acc + (blockIdx.x % kAccCopies) * kAccStride + t, accL[t]);
 		return;  // sc_post follows
 	}
 	if (gridDim.x == 1) {  // a single workgroup posts its own sums
-		if (threadIdx.x < 4 * (A.kmax + 1)) {
-			A.res[threadIdx.x] = accL[threadIdx.x];
-			if (A.sink) A.sink[threadIdx.x] = accL[threadIdx.x];
-		}
-		if (A.sink && threadIdx.x == 0) A.sink[kResSeq] = (uint32_t)A.skip1 | (A.mode == 2 ? 2u : 0u);
-		__threadfence_system();
-		__syncthreads();
-		if (threadIdx.x == 0) __hip_atomic_store(A.res + kResSeq, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+		post_words(A, t, t < nw ? accL[t] : 0u);
 		return;
 	}
 	// small grids (<= kAccCopies workgroups): workgroup b stores its sums into copy b with plain
 	// stores, the last one to finish XORs the gridDim.x copies and posts the points itself
-	const int nw = 4 * (A.kmax + 1);
-	if (threadIdx.x < nw) A.acc[blockIdx.x * kAccStride + threadIdx.x] = accL[threadIdx.x];
+	if (t < nw) A.acc[blockIdx.x * kAccStride + t] = accL[t];
 	uint32_t* last = accL + 4 * (kMaxD + 1);  // (a static __shared__ word cost a workgroup per CU)
 	__syncthreads();
-	if (threadIdx.x == 0)
+	if (t == 0)
 		// acq_rel: release orders this workgroup's stores before its count, acquire makes every other
 		// workgroup's stores visible to the last one
 		*last = __hip_atomic_fetch_add(A.acc + kAccCount, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
@@ -428,26 +314,32 @@ __device__ __forceinline__ void messages_run(const ScArgs& A, uint32_t* lds, uin
 	if (!*last) return;
 	__threadfence();
 	uint32_t* red = last + 1;  // 4 (kMaxD + 1) words
-	if (threadIdx.x < nw) red[threadIdx.x] = 0;
+	if (t < nw) red[t] = 0;
 	__syncthreads();
 	// every (copy, word) by one thread, XOR-reduced in LDS
-	for (int i = threadIdx.x; i < (int)gridDim.x * nw; i += kScThreads) {
+	for (int i = t; i < (int)gridDim.x * nw; i += kScThreads) {
 		const int b = i / nw, w = i - b * nw;
 		const uint32_t v = __hip_atomic_load(A.acc + b * kAccStride + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		if (v) atomicXor(red + w, v);
 	}
 	__syncthreads();
-	if (threadIdx.x < nw) {
-		A.res[threadIdx.x] = red[threadIdx.x];
-		if (A.sink) A.sink[threadIdx.x] = red[threadIdx.x];
-	}
-	if (A.sink && threadIdx.x == 0) A.sink[kResSeq] = (uint32_t)A.skip1 | (A.mode == 2 ? 2u : 0u);
-	__threadfence_system();
-	__syncthreads();
-	if (threadIdx.x == 0) __hip_atomic_store(A.res + kResSeq, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+	post_words(A, t, t < nw ? red[t] : 0u);
 }
 
-#endif  // BN_SC_FUSED
+// One (pair, point k) per group, k fastest: the kmax+1 groups of a pair run side by side, so the
+// pair's columns are read from HBM once and hit in cache for the other points.
+template <int MODE, int G>
+__global__ __launch_bounds__(kScThreads, kScMinWG) void sc_messages(ScArgs A) {
+	extern __shared__ uint32_t lds[];
+	uint32_t* accL = messages_init<G>(A, lds);
+	__syncthreads();
+	const int npts = A.kmax + 1 - A.skip1;
+	const size_t item = (size_t)blockIdx.x * Grp<G>::kGroups + threadIdx.x / G;
+	const size_t p = item / npts;
+	const int ki = (int)(item % npts);
+	const int k = (A.skip1 && ki >= 1) ? ki + 1 : ki;
+	messages_run<MODE, G>(A, lds, accL, p, k, p < A.n_pairs);
+}
 
 // Big grids: a one-wave kernel after sc_messages reduces the copies and posts the points (one
 // counter shared by thousands of workgroups serialised them: 2x the kernel time).
@@ -552,81 +444,6 @@ constexpr int kPairItemsPerWG = kScThreads / 2;
 constexpr size_t kPairMinItems = 384 * (size_t)kPairItemsPerWG;
 __device__ __forceinline__ uint32_t* pair_addr(uint32_t* slot, int w) { return slot + (w >> 6) * kPairRowWords + (w & 63); }
 
-#ifdef BN_SC_FUSED
-// One wave's 32 lane-pair folds. Item q < 32 of the wave folds batch lo_of(q) (nullptr: no item)
-// with the batch 2 A.n_pairs further on, in place. Lane t of the wave moves 16 B of item (t >> 5) + 2 i at
-// word (4 t) & 127 for i < 16: coalesced 512-B pieces.
-// (sc_fold_pair keeps its own copy of this body with one base pointer per wave: a per-item pointer
-// here made the product kernel 35 % slower, round 6)
-template <bool MAYBE_NULL, class LoOf>
-__device__ __forceinline__ void fold_pair_wave(const ScArgs& A, uint32_t* slot, int lane, LoOf lo_of) {
-	const int u = lane & 1;
-	uint4 la[16];
-#pragma unroll
-	for (int i = 0; i < 16; i++) {
-		const int w = 4 * lane + 256 * i;
-		const uint32_t* lo = lo_of(w >> 7);
-		uint4 b = make_uint4(0, 0, 0, 0);
-		la[i] = b;
-		if (!MAYBE_NULL || lo) {
-			b = *(const uint4*)(lo + 256 * A.n_pairs + (w & 127));  // old pair distance 2 hb'
-
-			la[i] = *(const uint4*)(lo + (w & 127));
-		}
-		*(uint4*)pair_addr(slot, w) = make_uint4(la[i].x ^ b.x, la[i].y ^ b.y, la[i].z ^ b.z, la[i].w ^ b.w);
-	}
-	wsync();
-	uint32_t* row = slot + lane * kPairRowWords;
-	uint32_t x[64], t[64];
-#pragma unroll
-	for (int i = 0; i < 64; i += 4) {
-		const uint4 v = *(const uint4*)(row + i);
-		x[i] = v.x, x[i + 1] = v.y, x[i + 2] = v.z, x[i + 3] = v.w;
-	}
-	wsync();  // every row read: the rows take lo
-#pragma unroll
-	for (int i = 0; i < 16; i++) *(uint4*)pair_addr(slot, 4 * lane + 256 * i) = la[i];
-#pragma unroll
-	for (int i = 0; i < 64; i++) t[i] = 0;
-#ifdef BN_DEV
-	if (!(A.dbg & 2))
-#endif
-	bsm6_fma_w2(x, A.r[2], A.r[3], t);  // a_u r1
-	const uint32_t m = 0u - (uint32_t)u;
-	uint32_t o[64];
-	{
-		uint32_t ah[32];
-		bs_alpha<5>(t + 32, ah);
-#pragma unroll
-		for (int i = 0; i < 32; i++) {
-			o[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)t[i], 0xB1, 0xF, 0xF, false) ^ (t[32 + i] & m);
-			o[32 + i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)t[32 + i], 0xB1, 0xF, 0xF, false) ^ ((t[i] ^ ah[i]) & m);
-		}
-	}
-	// (x opaque: the compiler would otherwise share the two products' data-side sums)
-#pragma unroll
-	for (int i = 0; i < 64; i++) asm volatile("" : "+v"(x[i]));
-#ifdef BN_DEV
-	if (!(A.dbg & 2))
-#endif
-	bsm6_fma_w2(x, A.r[0], A.r[1], o);  // + a_u r0
-	wsync();
-#pragma unroll
-	for (int i = 0; i < 64; i += 4) {
-		const uint4 v = *(const uint4*)(row + i);
-		*(uint4*)(row + i) = make_uint4(o[i] ^ v.x, o[i + 1] ^ v.y, o[i + 2] ^ v.z, o[i + 3] ^ v.w);
-	}
-	wsync();
-#pragma unroll
-	for (int i = 0; i < 16; i++) {
-		const int w = 4 * lane + 256 * i;
-		uint32_t* lo = lo_of(w >> 7);
-		if (!MAYBE_NULL || lo) *(uint4*)(lo + (w & 127)) = *(const uint4*)pair_addr(slot, w);
-	}
-}
-
-#endif  // BN_SC_FUSED
-
 __global__ __launch_bounds__(kScThreads, kScMinWG) void sc_fold_pair(ScArgs A) {
 	extern __shared__ uint32_t lds[];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = lane & 1;
@@ -694,44 +511,6 @@ __global__ __launch_bounds__(kScThreads, kScMinWG) void sc_fold_pair(ScArgs A) {
 	}
 }
 
-#ifdef BN_SC_FUSED
-// Round i's fold fused with round i + 1's messages (the QM31 sibling's
-// qm_fold_messages in GF(2^128) form). A work-group owns P = kGroups / npts consecutive pairs
-// p0 .. p0 + P - 1 of the folded columns (pair distance hb' = A.n_pairs). Phase 1 folds the 2 P d
-// batches they consist of, p' and p' + hb' of every column (old pairs (b, b + 2 hb')), on lane
-// pairs as sc_fold_pair, and writes them in place. Phase 2 runs the
-// messages of those P pairs on the quads as sc_messages, reading the batches the work-group has
-// just written (L2) instead of a second kernel reading them back from HBM; one launch per round
-// instead of two. No other work-group reads what this one writes: pair p' reads old batches p',
-// p' + hb', p' + 2 hb', p' + 3 hb' and writes p', p' + hb' only.
-__global__ __launch_bounds__(kScThreads, kScMinWG) void sc_fold_msgs(ScArgs A) {
-	extern __shared__ uint32_t lds[];
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const int npts = A.kmax + 1 - A.skip1;
-	const int P = A.fm_p;
-	const size_t p0 = (size_t)blockIdx.x * P;
-	const size_t hbn = A.n_pairs;
-	uint32_t* accL = messages_init<4>(A, lds);
-	// phase 1: item v of column j (v < 2 P) folds batch p0 + v (v < P) or hb' + p0 + v - P
-	const int items = 2 * P * A.d;
-	if (32 * wave < items) {
-		fold_pair_wave<true>(A, lds + wave * kPairWaveWords, lane, [&](int q) -> uint32_t* {
-			const int it = 32 * wave + q;
-			if (it >= items) return nullptr;
-			const int j = (int)__umulhi((uint32_t)it, A.fm_magic), v = it - j * 2 * P;
-			const size_t pp = p0 + (size_t)(v < P ? v : v - P);
-			if (pp >= hbn) return nullptr;
-			return A.cols + (size_t)j * A.col_stride + 128 * (v < P ? pp : pp + hbn);
-		});
-	}
-	// every fold of the work-group is in memory (L2) and the fold's LDS rows are free
-	__syncthreads();
-	const int qw = threadIdx.x / 4;
-	const int lp = qw / npts, ki = qw - lp * npts;
-	const int k = (A.skip1 && ki >= 1) ? ki + 1 : ki;
-	messages_run<0, 4>(A, lds, accL, p0 + (size_t)lp, k, lp < P && p0 + (size_t)lp < hbn);
-}
-#endif  // BN_SC_FUSED
 // ---------------------------------------------------------------------------------------
 // Round server for the last rounds (at most kServerMaxCur evaluations per column left): ONE
 // resident 768-thread workgroup runs every remaining round by itself. It waits for the host's
@@ -817,19 +596,7 @@ __device__ __forceinline__ void srv_messages(const ScArgs& a, const uint32_t (*k
 			if (l < 4) {
 				uint32_t lo[32], hi[32];
 				load_pair<MODE>(a, j, p, l, lo, hi, emask);
-				if (k == 1) {
-#pragma unroll
-					for (int i = 0; i < 32; i++) lo[i] = hi[i];
-				} else if (k > 1) {
-#pragma unroll
-					for (int i = 0; i < 32; i++) hi[i] ^= lo[i];
-					if (a.kmax <= 3)
-						mul_23(0u - (uint32_t)(k & 1), hi);
-					else
-						mul_small(kcol[k], hi, hi);
-#pragma unroll
-					for (int i = 0; i < 32; i++) lo[i] ^= hi[i];
-				}
+				point_at(a, kcol, k, lo, hi);
 				sst(S, (j == 0 ? 0 : 4) + l, lo);
 			}
 			if (j > 0) grp_mul<kSrvG, false>(S, nullptr, l);
@@ -1011,6 +778,32 @@ namespace {
 using namespace bn;
 using namespace bn::quad;
 
+// GF(2^4) products k * 2^a (ScArgs::kcol, SrvArgs::kcol), tabulated once (36 recursive tower
+// products per launch were ~1 us of host time on every round's critical path)
+struct KCol {
+	uint32_t v[kMaxD + 1][4];
+	KCol() {
+		for (int k = 0; k <= kMaxD; k++)
+			for (int a = 0; a < 4; a++) v[k][a] = (uint32_t)tw_mul((uint64_t)k, 1ull << a, 2);
+	}
+};
+const KCol& kcol_table() {
+	static const KCol kc;
+	return kc;
+}
+
+// Every kernel that takes dynamic LDS (sc_common_init raises the limit of each entry, sc_launch
+// launches nothing else but sc_post): the messages by [tier][mode], the folds by [tier][mode]
+// (tier 0, 1, 2 = 4-, 16-, 64-lane products; folds have no 64-lane tier), the two big-mode folds.
+constexpr int kMsgKernels = 0, kFoldKernels = 9, kFoldCoalKernel = 15, kFoldPairKernel = 16;
+const void* const kScKernels[17] = {
+	(const void*)sc_messages<0, 4>,  (const void*)sc_messages<1, 4>,  (const void*)sc_messages<2, 4>,
+	(const void*)sc_messages<0, 16>, (const void*)sc_messages<1, 16>, (const void*)sc_messages<2, 16>,
+	(const void*)sc_messages<0, 64>, (const void*)sc_messages<1, 64>, (const void*)sc_messages<2, 64>,
+	(const void*)sc_fold<0, 4>,      (const void*)sc_fold<1, 4>,      (const void*)sc_fold<2, 4>,
+	(const void*)sc_fold<0, 16>,     (const void*)sc_fold<1, 16>,     (const void*)sc_fold<2, 16>,
+	(const void*)sc_fold_coal,       (const void*)sc_fold_pair};
+
 int sc_launch(bn_sumcheck* sc, bool fold, const uint32_t* r) {
 	ScArgs A{};
 	A.cols = sc->cols;
@@ -1044,17 +837,7 @@ int sc_launch(bn_sumcheck* sc, bool fold, const uint32_t* r) {
 		A.dbg = dbg;
 	}
 #endif
-	// GF(2^4) products k * 2^a, tabulated once (36 recursive tower products per launch were ~1 us of
-	// host time on every round's critical path)
-	struct KCol {
-		uint32_t v[kMaxD + 1][4];
-		KCol() {
-			for (int k = 0; k <= kMaxD; k++)
-				for (int a = 0; a < 4; a++) v[k][a] = (uint32_t)tw_mul((uint64_t)k, 1ull << a, 2);
-		}
-	};
-	static const KCol kc;
-	memcpy(A.kcol, kc.v, sizeof A.kcol);
+	memcpy(A.kcol, kcol_table().v, sizeof A.kcol);
 	// one item per lane group: fold (column, pair), messages (pair, point)
 	const size_t items = fold ? (size_t)sc->d * A.n_pairs : A.n_pairs * (size_t)(A.kmax + 1 - A.skip1);
 	size_t hex_max = kHexMaxItems, wide_max = kWideMaxItems, post_max = kPostInKernelMaxWG;
@@ -1084,82 +867,16 @@ int sc_launch(bn_sumcheck* sc, bool fold, const uint32_t* r) {
 #endif
 	if (pair) {  // lane-pair products with a scalar challenge (sc_fold_pair)
 		grid = (items + kPairItemsPerWG - 1) / kPairItemsPerWG;
-		BN_HIP(hipLaunchKernel((const void*)sc_fold_pair, dim3((unsigned)grid), dim3(kScThreads), args,
+		BN_HIP(hipLaunchKernel(kScKernels[kFoldPairKernel], dim3((unsigned)grid), dim3(kScThreads), args,
 		                       sizeof(uint32_t) * 4 * kPairWaveWords, sc->stream));
 		return BN_OK;
 	}
-	const void* fns[3][2][3] = {
-		{{(const void*)sc_messages<0, 4>, (const void*)sc_messages<1, 4>, (const void*)sc_messages<2, 4>},
-		 {coal ? (const void*)sc_fold_coal : (const void*)sc_fold<0, 4>, (const void*)sc_fold<1, 4>, (const void*)sc_fold<2, 4>}},
-		{{(const void*)sc_messages<0, 16>, (const void*)sc_messages<1, 16>, (const void*)sc_messages<2, 16>},
-		 {(const void*)sc_fold<0, 16>, (const void*)sc_fold<1, 16>, (const void*)sc_fold<2, 16>}},
-		{{(const void*)sc_messages<0, 64>, (const void*)sc_messages<1, 64>, (const void*)sc_messages<2, 64>},
-		 {(const void*)sc_fold<0, 16>, (const void*)sc_fold<1, 16>, (const void*)sc_fold<2, 16>}}};  // (not used)
+	const void* fn = kScKernels[coal ? kFoldCoalKernel : (fold ? kFoldKernels : kMsgKernels) + 3 * tier + A.mode];
 	A.post = grid <= post_max;
 	const size_t lds = tier == 2 ? lds_bytes<64>() : tier == 1 ? lds_bytes<16>() : lds_bytes<4>();
-	BN_HIP(hipLaunchKernel(fns[tier][fold ? 1 : 0][A.mode], dim3((unsigned)grid), dim3(kScThreads), args, lds, sc->stream));
+	BN_HIP(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(kScThreads), args, lds, sc->stream));
 	if (!fold && !A.post) BN_HIP(hipLaunchKernel((const void*)sc_post, dim3(1), dim3(64), args, 0, sc->stream));
 	return BN_OK;
-}
-
-// Round i's fold with r fused into round i + 1's messages (sc_fold_msgs): the big rounds whose
-// messages run on quads. Called after move_to_next_round has halved cur and updated the claim state.
-// Measured slower than separate fold + messages launches on c4 (d = 3: 3.59-3.67 vs 3.40-3.44 ms,
-// DESIGN.md section 10): the batches a work-group folds leave L2 before its messages phase reads
-// them, so the product keeps the two launches; -DBN_SC_FUSED builds the fused path (experiments).
-#ifdef BN_SC_FUSED
-constexpr bool kFusedFold = true;
-#else
-constexpr bool kFusedFold = false;
-#endif
-bool fused_eligible(const bn_sumcheck* sc) {
-	if (!kFusedFold || !sc->eager || sc->cur < 64 || (sc->world > 1 && sc->cur <= 32)) return false;
-	const int npts = sc->d + 1 - ((sc->have_claim || sc->claim_pending) ? 1 : 0);
-	return (sc->cur / 64) * (size_t)npts > kHexMaxItems && npts <= Grp<4>::kGroups;
-}
-
-int launch_fused(bn_sumcheck* sc, const uint32_t* r) {
-#ifndef BN_SC_FUSED
-	(void)sc, (void)r;
-	BN_FAIL(BN_ERR_UNSUPPORTED, "fused fold + messages: experiment builds only (-DBN_SC_FUSED)");
-#else
-	ScArgs A{};
-	A.cols = sc->cols;
-	A.col_stride = sc->col_words;
-	A.d = sc->d;
-	A.mode = 0;
-	A.n_pairs = sc->cur / 64;  // pairs of the folded columns (the fold's pairs are 2 n_pairs apart)
-	A.hb = A.n_pairs;
-	A.kmax = sc->d;
-	A.skip1 = (sc->have_claim || sc->claim_pending) ? 1 : 0;
-	A.res = sc->d_res;
-	A.sink = sc->sink;
-	A.seq = ++sc->seq;
-	A.acc = sc->acc + kAccSet * sc->par;
-	A.clr = sc->acc + kAccSet * (1 - sc->par);
-	memcpy(A.r, r, 16);
-#ifdef BN_DEV
-	{
-		static const int dbg = getenv("BN_SC_DBG") ? atoi(getenv("BN_SC_DBG")) : 0;
-		A.dbg = dbg;
-	}
-#endif
-	for (int k = 0; k <= kMaxD; k++)
-		for (int a = 0; a < 4; a++) A.kcol[k][a] = (uint32_t)tw_mul((uint64_t)k, 1ull << a, 2);
-	const int npts = A.kmax + 1 - A.skip1;
-	const size_t P = Grp<4>::kGroups / npts;
-	A.fm_p = (int)P;
-	A.fm_magic = (uint32_t)(((1ull << 32) + 2 * P - 1) / (2 * P));
-	const size_t grid = (A.n_pairs + P - 1) / P;
-	A.post = grid <= kPostInKernelMaxWG;
-	void* args[] = {&A};
-	const size_t lds = std::max(lds_bytes<4>(), sizeof(uint32_t) * 4 * kPairWaveWords);
-	BN_HIP(hipLaunchKernel((const void*)sc_fold_msgs, dim3((unsigned)grid), dim3(kScThreads), args, lds, sc->stream));
-	if (!A.post) BN_HIP(hipLaunchKernel((const void*)sc_post, dim3(1), dim3(64), args, 0, sc->stream));
-	sc->par ^= 1;
-	sc->msgs_queued = true;
-	return BN_OK;
-#endif
 }
 
 #ifdef BN_DEV
@@ -1203,8 +920,7 @@ int server_launch(bn_sumcheck* sc, size_t cur, uint32_t seq, uint32_t ticket) {
 	}
 #endif
 	((volatile uint32_t*)sc->h_ctl)[kCtlExit] = kSrvRunning;
-	for (int k = 0; k <= kMaxD; k++)
-		for (int a = 0; a < 4; a++) P.kcol[k][a] = (uint32_t)tw_mul((uint64_t)k, 1ull << a, 2);
+	memcpy(P.kcol, kcol_table().v, sizeof P.kcol);
 	void* args[] = {&P};
 	BN_HIP(hipLaunchKernel((const void*)sc_server, dim3(1), dim3(kSrvThreads), args, srv_lds_bytes(), sc->stream));
 	sc->server = true;
@@ -1290,14 +1006,8 @@ int sc_common_init(bn_sumcheck* sc) {
 #ifdef BN_DEV
 	if (const char* e = getenv("BN_SC_SERVER_MAX_CUR")) sc->server_max_cur = (size_t)atol(e);
 #endif
-	const void* fns[17] = {(const void*)sc_messages<0, 4>,  (const void*)sc_messages<1, 4>,  (const void*)sc_messages<2, 4>,
-						   (const void*)sc_fold<0, 4>,      (const void*)sc_fold<1, 4>,      (const void*)sc_fold<2, 4>,
-						   (const void*)sc_messages<0, 16>, (const void*)sc_messages<1, 16>, (const void*)sc_messages<2, 16>,
-						   (const void*)sc_fold<0, 16>,     (const void*)sc_fold<1, 16>,     (const void*)sc_fold<2, 16>,
-						   (const void*)sc_messages<0, 64>, (const void*)sc_messages<1, 64>, (const void*)sc_messages<2, 64>,
-						   (const void*)sc_fold_coal, (const void*)sc_fold_pair};
 	const int lds_max = (int)std::max(lds_bytes<4>(), std::max(lds_bytes<16>(), lds_bytes<64>()));
-	for (const void* f : fns) BN_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+	for (const void* f : kScKernels) BN_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
 	return BN_OK;
 }
 
@@ -1536,10 +1246,8 @@ extern "C" int bn_sumcheck_set_shard(bn_sumcheck* sc, int rank, int world) {
 	BN_CHECK_ARG(n >= (size_t)32 * world, "need at least one 32-element batch per rank");
 	if (world == 1) return BN_OK;
 	DeviceScope ds(sc->device);
-	if (!sc->prepared) {  // a staged prover transposes on first use
-		const int prc = sc_prepare(sc);
-		if (prc != BN_OK) return prc;
-	}
+	const int prc = sc_prepare(sc);  // a staged prover transposes on first use
+	if (prc != BN_OK) return prc;
 	// keep the batches b with b mod world == rank, in order
 	const size_t nb_local = n / 32 / world;
 	uint32_t* local = nullptr;
@@ -1627,10 +1335,8 @@ extern "C" int bn_sumcheck_round_messages(bn_sumcheck* sc, uint32_t* sum, uint32
 	BN_CHECK_ARG(sc && sum && points, "NULL argument");
 	BN_CHECK_ARG(!(sc->world > 1 && sc->cur <= 32), "shard exhausted: gather (export_shard/import_gathered) first");
 	DeviceScope ds(sc->device);
-	if (!sc->prepared) {  // a staged prover transposes on first use
-		const int prc = sc_prepare(sc);
-		if (prc != BN_OK) return prc;
-	}
+	const int prc = sc_prepare(sc);  // a staged prover transposes on first use
+	if (prc != BN_OK) return prc;
 	if (!sc->msgs_queued && sc->server) {
 		// this round was read already and the server is waiting for the next challenge (no launch
 		// may queue behind it): the same messages again
@@ -1689,10 +1395,8 @@ extern "C" int bn_sumcheck_round_messages_sink(bn_sumcheck* sc) {
 	BN_CHECK_ARG(!(sc->world > 1 && sc->cur <= 32), "shard exhausted: gather (export_shard/import_gathered) first");
 	BN_CHECK_ARG(!sc->server, "the round server is running: read this round with bn_sumcheck_round_messages");
 	DeviceScope ds(sc->device);
-	if (!sc->prepared) {
-		const int prc = sc_prepare(sc);
-		if (prc != BN_OK) return prc;
-	}
+	const int prc = sc_prepare(sc);
+	if (prc != BN_OK) return prc;
 	if (!sc->msgs_queued) {
 		const int rc = queue_messages(sc);
 		if (rc != BN_OK) return rc;
@@ -1713,56 +1417,36 @@ extern "C" int bn_sumcheck_move_to_next_round(bn_sumcheck* sc, const uint32_t* c
 	BN_CHECK_ARG(sc->cur >= 2, "no variables left to fold");
 	BN_CHECK_ARG(!(sc->world > 1 && sc->cur <= 32), "shard exhausted: gather (export_shard/import_gathered) first");
 	DeviceScope ds(sc->device);
-	if (!sc->prepared) {  // a staged prover transposes on first use
-		const int prc = sc_prepare(sc);
-		if (prc != BN_OK) return prc;
-	}
+	int rc = sc_prepare(sc);  // a staged prover transposes on first use
+	if (rc != BN_OK) return rc;
 	const bool to_server = sc->server || server_eligible(sc);
 	// no sync: the fold is ordered before the next round's messages on the prover's stream
 	sc->have_claim = false;  // a claim not consumed by this round's messages is stale now
 	sc->claim_pending = sc->have_pts && sc->derive_p1;
-	sc->cur /= 2;
-	const bool fused = !to_server && fused_eligible(sc);  // decided on the folded size
-	sc->cur *= 2;
-	if (!to_server && !fused) {  // (a fold launch does not read the claim state)
-		int rc = sc_launch(sc, true, challenge);
-		if (rc != BN_OK) return rc;
-	}
+	if (!to_server && (rc = sc_launch(sc, true, challenge)) != BN_OK) return rc;  // (a fold launch does not read the claim state)
 	if (sc->claim_pending) memcpy(sc->pending_r, challenge, 16);
 	sc->have_pts = false;
 	sc->read_this_round = false;
-	if (fused) {
-		sc->cur /= 2;
-		sc->round++;
-		sc->sharded_used = true;
-		sc->msgs_queued = false;  // a queued, unread messages kernel ran before the fold: dropped
-		return launch_fused(sc, challenge);
-	}
 	if (to_server) {
 		// the round server folds and computes the next round's messages (p(1) skipped when the
 		// claim is derived; never for the final evaluation, which the server decides itself)
 		if (sc->server && sc->msgs_queued) {
 			// the previous challenge's messages were not read: let them land first (one ticket at a
 			// time, so a relaunched server never misses an overwritten challenge)
-			const int wrc = wait_posted(sc);
-			if (wrc != BN_OK) return wrc;
+			if ((rc = wait_posted(sc)) != BN_OK) return rc;
 		}
 		if (!sc->server || ((volatile uint32_t*)sc->h_ctl)[kCtlExit] == sc->ticket) {
-			const int rc = server_launch(sc, sc->cur, sc->seq + 1, sc->ticket + 1);
-			if (rc != BN_OK) return rc;
+			if ((rc = server_launch(sc, sc->cur, sc->seq + 1, sc->ticket + 1)) != BN_OK) return rc;
 		}
 		server_post(sc, challenge, sc->claim_pending && sc->cur / 2 >= 2);
-		sc->cur /= 2;
-		sc->round++;
-		sc->sharded_used = true;
-		sc->msgs_queued = true;
-		return BN_OK;
 	}
 	sc->cur /= 2;
 	sc->round++;
 	sc->sharded_used = true;
-	sc->msgs_queued = false;  // a queued, unread messages kernel ran before the fold: dropped
-	if (sc->eager && !(sc->world > 1 && sc->cur <= 32)) return queue_messages(sc);
+	// the server's post is this round's queued messages; on the plain path a queued, unread messages
+	// kernel ran before the fold and is dropped
+	sc->msgs_queued = to_server;
+	if (!to_server && sc->eager && !(sc->world > 1 && sc->cur <= 32)) return queue_messages(sc);
 	return BN_OK;
 }
 

@@ -55,8 +55,9 @@ def test_null_arguments_rejected():
 
 
 def test_product_library_has_no_experiment_kernels():
-    """Experiments measured and not kept live only in the development / experiment builds (BN_DEV,
-    -DBN_SC_FUSED): the product library the driver loads carries none of their kernels."""
+    """Experiments measured and not kept live only in the development build (BN_DEV) or, like the
+    fused sumcheck fold + messages kernel sc_fold_msgs, have left the tree:
+    the product library the driver loads carries none of their kernels."""
     with open(B.LIB_PATH, "rb") as f:
         blob = f.read()
     for name in (b"antt_bs_persist3", b"antt_rr_mid_pf", b"antt_rr_pass_persist", b"sc_fold_msgs"):

@@ -65,10 +65,11 @@ def test_sumcheck_transcript_quad_path(n, d, dev):
 
 @pytest.mark.parametrize("n,d,full_points", [(19, 3, False), (19, 2, False), (19, 2, True)])
 def test_sumcheck_transcript_fused_fold_messages(n, d, full_points, dev, monkeypatch):
-    # N = 19 transcripts against the oracle, every round's sum and points. Round 1 (2^18
-    # evaluations per column left, with and without the claim-derived point 1) is the first round
-    # whose fold the -DBN_SC_FUSED experiment build runs inside the messages launch (sc_fold_msgs;
-    # this test was green on that build too).
+    # N = 19 transcripts against the oracle, every round's sum and points, with and without the
+    # claim-derived point 1. The only transcript test whose first rounds take the lane-pair fold
+    # (sc_fold_pair) together with quad messages and sc_post. (Named after the round-6 experiment
+    # that fused such a round's fold into the next messages launch; that kernel was measured slower
+    # and removed)
     if full_points:
         monkeypatch.setenv("BN_SUMCHECK_FULL_POINTS", "1")
     ev, ch = _case(n, d, 1900 + 10 * d + full_points)
