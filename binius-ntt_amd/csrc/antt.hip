@@ -210,6 +210,9 @@ bool bs_supports(const bn_antt_plan* plan);
 int bs_prepare(bn_antt_plan* plan);
 int bs_time_passes(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, int reps,
                    hipStream_t st, float* ms, int max_passes, int* n_out);
+// Inverse transform (antt_inv.hip): compact tiles for variant 0, bitsliced LDS tiles otherwise.
+int launch_inv_v0(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, int coset, hipStream_t st);
+int launch_inv_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, int coset, size_t batch, hipStream_t st);
 
 // Kernel variants: 0 compact tiles (log_h < 12), 1 bitsliced LDS tiles (antt_bs_pass), 4 bitsliced
 // register tiles (antt_rr_pass), 5 = 4 for the passes whose twiddles all lie in GF(2^8) and 1 for
@@ -349,6 +352,61 @@ extern "C" int bn_antt_forward_host(bn_antt_plan* p, const void* in, size_t in_e
 		return rc;
 	}
 	BN_HIP(hipMemcpyAsync(out, p->h_dev_out, out_bytes, hipMemcpyDeviceToHost, p->own_stream));
+	BN_HIP(hipStreamSynchronize(p->own_stream));
+	(void)hipSetDevice(dev_prev);
+	return BN_OK;
+}
+
+static int inverse_device_impl(bn_antt_plan* p, const void* d_in, void* d_out, int coset, size_t batch, hipStream_t st) {
+	if (p->variant != 0) return launch_inv_bs(p, (const uint32_t*)d_in, (uint32_t*)d_out, coset, batch, st);
+	const size_t n_words = ((size_t)1 << p->log_h) * p->limbs;
+	for (size_t b = 0; b < batch; b++) {
+		int rc = launch_inv_v0(p, (const uint32_t*)d_in + b * n_words, (uint32_t*)d_out + b * n_words, coset, st);
+		if (rc != BN_OK) return rc;
+	}
+	return BN_OK;
+}
+
+extern "C" int bn_antt_inverse_device(bn_antt_plan* p, const void* d_in, void* d_out, int coset, size_t batch,
+                                      void* stream) {
+	BN_CHECK_ARG(p != nullptr, "plan is NULL");
+	BN_CHECK_ARG(d_in != nullptr && d_out != nullptr, "device buffers must be non-NULL");
+	BN_CHECK_ARG(batch >= 1, "batch must be >= 1");
+	BN_CHECK_ARG(coset >= 0 && coset < (1 << p->log_rate), "coset must be in [0, 2^%d) (got %d)", p->log_rate, coset);
+	const size_t bytes = ((size_t)1 << p->log_h) * p->limbs * 4 * batch;
+	const char* a = (const char*)d_in;
+	const char* b = (const char*)d_out;
+	BN_CHECK_ARG(a + bytes <= b || b + bytes <= a, "d_in and d_out must not overlap");
+	int dev_prev = 0;
+	(void)hipGetDevice(&dev_prev);
+	if (dev_prev != p->device) BN_HIP(hipSetDevice(p->device));
+	int rc = inverse_device_impl(p, d_in, d_out, coset, batch, (hipStream_t)stream);
+	if (dev_prev != p->device) (void)hipSetDevice(dev_prev);
+	return rc;
+}
+
+extern "C" int bn_antt_inverse_host(bn_antt_plan* p, const void* in, size_t in_elems, int coset, void* out) {
+	BN_CHECK_ARG(p != nullptr, "plan is NULL");
+	BN_CHECK_ARG(in != nullptr && out != nullptr, "host buffers must be non-NULL");
+	BN_CHECK_ARG(in_elems == ((size_t)1 << p->log_h), "input has %zu elements, plan expects 2^%d", in_elems, p->log_h);
+	BN_CHECK_ARG(coset >= 0 && coset < (1 << p->log_rate), "coset must be in [0, 2^%d) (got %d)", p->log_rate, coset);
+	int dev_prev = 0;
+	(void)hipGetDevice(&dev_prev);
+	BN_HIP(hipSetDevice(p->device));
+	const size_t bytes = in_elems * p->limbs * 4;
+	if (!p->h_dev_in) {
+		// the forward staging buffers: the inverse needs 2^log_h elements of each
+		BN_HIP(hipMalloc(&p->h_dev_in, bytes));
+		BN_HIP(hipMalloc(&p->h_dev_out, bytes << p->log_rate));
+	}
+	if (!p->own_stream) BN_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
+	BN_HIP(hipMemcpyAsync(p->h_dev_in, in, bytes, hipMemcpyHostToDevice, p->own_stream));
+	int rc = inverse_device_impl(p, p->h_dev_in, p->h_dev_out, coset, 1, p->own_stream);
+	if (rc != BN_OK) {
+		(void)hipSetDevice(dev_prev);
+		return rc;
+	}
+	BN_HIP(hipMemcpyAsync(out, p->h_dev_out, bytes, hipMemcpyDeviceToHost, p->own_stream));
 	BN_HIP(hipStreamSynchronize(p->own_stream));
 	(void)hipSetDevice(dev_prev);
 	return BN_OK;

@@ -22,6 +22,7 @@ struct bn_antt_plan {
 	uint32_t* scratch = nullptr;   // pass-intermediate buffer (variant-specific)
 	size_t scratch_bytes = 0;
 	std::vector<unsigned char> bs_passes;  // variant-1 pass tables (antt_bs.hip), built on first use
+	int inv_prepared = 0;  // LDS attribute of the bitsliced inverse kernels set (antt_inv.hip)
 	hipStream_t own_stream = nullptr;
 	// host-apply staging
 	void* h_dev_in = nullptr;

@@ -42,6 +42,23 @@ public:
 		ulvt::bn_check(bn_antt_forward_device(plan, d_in, d_out, batch, stream));
 	}
 
+	// Inverse (no reference counterpart): evaluations on coset `coset` (block `coset` of apply()'s
+	// output) back to coefficients. Returns false, with no other effect, unless input.size ==
+	// 2^log_h, input.order == IN_ORDER and output holds 2^log_h elements; otherwise writes 2^log_h
+	// elements, sets output.order = IN_ORDER and returns after a full sync.
+	bool inverse(const NTTData<T>& input, NTTData<T>& output, int coset = 0) {
+		if (input.size != ((size_t)1 << ntt_conf.log_h) || input.order != DataOrder::IN_ORDER) return false;
+		if (output.size < ((size_t)1 << ntt_conf.log_h)) return false;
+		ulvt::bn_check(bn_antt_inverse_host(plan, input.data.get(), input.size, coset, output.data.get()));
+		output.order = DataOrder::IN_ORDER;
+		return true;
+	}
+
+	// `batch` device-resident inverse transforms on one coset, asynchronous on `stream`.
+	void inverse_device(const void* d_in, void* d_out, int coset = 0, size_t batch = 1, void* stream = nullptr) {
+		ulvt::bn_check(bn_antt_inverse_device(plan, d_in, d_out, coset, batch, stream));
+	}
+
 	// 0: compact tiles, per-butterfly twiddles (default for log_h < 12); 1: bitsliced LDS tiles;
 	// 4: bitsliced register tiles; 5: 4 for the GF(2^8)-twiddle passes, 1 for the others (default
 	// for log_h >= 12)

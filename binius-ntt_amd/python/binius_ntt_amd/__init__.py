@@ -61,6 +61,8 @@ def lib():
         "bn_antt_plan_destroy": (i32, [vp]),
         "bn_antt_forward_host": (i32, [vp, vp, sz, vp]),
         "bn_antt_forward_device": (i32, [vp, vp, vp, sz, vp]),
+        "bn_antt_inverse_device": (i32, [vp, vp, vp, i32, sz, vp]),
+        "bn_antt_inverse_host": (i32, [vp, vp, sz, i32, vp]),
         "bn_antt_get_subspace_evals": (i32, [vp, u32p, sz]),
         "bn_antt_plan_query": (i32, [vp, i32, ctypes.POINTER(ctypes.c_int64)]),
         "bn_antt_plan_set_variant": (i32, [vp, i32]),
@@ -265,6 +267,33 @@ class AdditiveNTT:
         _check_device_tensor(d_in, n, "d_in")
         _check_device_tensor(d_out, n << self.conf.log_rate, "d_out")
         _check(lib().bn_antt_forward_device(self._plan, _ptr(d_in), _ptr(d_out), batch,
+                                            _stream(stream, self.conf.device)))
+
+    def inverse(self, inp, out, coset=0):
+        """Evaluations on coset `coset` (block `coset` of apply()'s output) back to coefficients;
+        no reference counterpart. False (no other effect) unless inp.size == 2^log_h and
+        inp.order == IN_ORDER; fills out with 2^log_h elements synchronously."""
+        n = 1 << self.conf.log_h
+        if inp.size != n or inp.order != DataOrder.IN_ORDER:
+            return False
+        src = np.ascontiguousarray(inp.data, dtype=np.uint32)
+        assert src.size == n * self.limbs
+        dst = out.data
+        if dst.size != n * self.limbs:
+            dst = np.zeros((n,) if self.limbs == 1 else (n, self.limbs), np.uint32)
+        _check(lib().bn_antt_inverse_host(self._plan, src.ctypes.data, n, coset, dst.ctypes.data))
+        out.data = dst
+        out.size = n
+        out.order = DataOrder.IN_ORDER
+        return True
+
+    def inverse_device(self, d_in, d_out, coset=0, batch=1, stream=None):
+        """Device-resident inverse transform(s), every one on coset `coset`; async on `stream`
+        (default: torch's current stream of the plan's device). d_in is left untouched."""
+        n = (1 << self.conf.log_h) * self.limbs * batch
+        _check_device_tensor(d_in, n, "d_in")
+        _check_device_tensor(d_out, n, "d_out")
+        _check(lib().bn_antt_inverse_device(self._plan, _ptr(d_in), _ptr(d_out), coset, batch,
                                             _stream(stream, self.conf.device)))
 
     def subspace_evals(self):

@@ -69,6 +69,20 @@ int bn_antt_forward_host(bn_antt_plan* plan, const void* in, size_t in_elems, vo
  * d_in and d_out must not overlap. Asynchronous on `stream` (a hipStream_t, may be 0). */
 int bn_antt_forward_device(bn_antt_plan* plan, const void* d_in, void* d_out, size_t batch, void* stream);
 
+/* Inverse transform on the device (no reference counterpart: the reference transforms in one
+ * direction only). With F_c(x) block `coset` of bn_antt_forward_device's output for input x
+ * (elements [coset*2^log_h, (coset+1)*2^log_h)), writes the unique x with F_c(x) = y: evaluations
+ * on one coset, in order, back to novel-basis coefficients, bit-exact. `batch` independent
+ * transforms on the same coset; transform b reads d_in + b*2^log_h elements and writes
+ * d_out + b*2^log_h elements. d_in is not written; d_in and d_out must not overlap;
+ * 0 <= coset < 2^log_rate (BN_ERR_INVALID otherwise, nothing is launched). Asynchronous on
+ * `stream`. Variant 0 runs compact tiles, variants 1, 4 and 5 bitsliced LDS tiles. */
+int bn_antt_inverse_device(bn_antt_plan* plan, const void* d_in, void* d_out, int coset, size_t batch, void* stream);
+/* The same with host buffers (no reference counterpart), synchronous, staged through the plan's
+ * own stream like bn_antt_forward_host. in_elems must equal 2^log_h (BN_ERR_INVALID with no other
+ * effect otherwise); `out` receives 2^log_h elements. */
+int bn_antt_inverse_host(bn_antt_plan* plan, const void* in, size_t in_elems, int coset, void* out);
+
 /* Copies the plan's normalised subspace-evaluation table s[i][j] (GF(2^32) values,
  * log_h rows x (log_h+log_rate-1) columns, row-major) to host memory. */
 int bn_antt_get_subspace_evals(const bn_antt_plan* plan, uint32_t* out, size_t out_words);

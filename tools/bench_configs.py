@@ -19,6 +19,9 @@ qm  QM31 sumcheck (prime-field sibling), two columns of 2^N Q
     composition: all N rounds (round messages + fold, one host round trip per round as in
     sumcheck.cuh:46-96) on device-resident columns; evals/s = 2^N / t (wall clock, setup upload
     excluded as the reference's benchmarking timer does).
+intt (only with --only intt) inverse additive NTT, GF(2^128), r = 0, 2^20 and 2^24: the inverse
+    next to the forward under set_variant(1) (the same products and LDS traffic) and the forward
+    default, all three in one process, ms per transform.
 Every line is one JSON object.
 """
 import argparse
@@ -109,6 +112,28 @@ def ntt_line(dev, out, cfg, log_h, batch):
     out({"config": cfg, "workload": "%d x 2^%d-point GF(2^128) additive NTT (r=0)" % (batch, log_h),
          "value": elems / (ms * 1e-3), "unit": "elements/s", "ms": ms,
          "hbm_gbps_algorithmic": 32.0 * elems / (ms * 1e-3) / 1e9})
+
+
+def intt_line(dev, out, log_h):
+    import torch
+    import binius_ntt_amd as B
+    n = 1 << log_h
+    g = np.random.default_rng(5)
+    x = torch.from_numpy(g.integers(0, 2**32, size=4 * n, dtype=np.uint64).astype(np.uint32).view(np.int32)).to(dev)
+    y = torch.empty_like(x)
+    ntt = B.AdditiveNTT(B.AdditiveNTTConf(log_h, 0, B.FanPaarTowerField(7), device=dev.index or 0))
+    st = torch.cuda.current_stream(dev)
+    default = ntt.variant()
+    ms_inv = ev_time(lambda: ntt.inverse_device(x, y, stream=st), 10, st)
+    ntt.set_variant(1)
+    ms_fwd1 = ev_time(lambda: ntt.forward_device(x, y, stream=st), 10, st)
+    ntt.set_variant(default)
+    ms_fwd = ev_time(lambda: ntt.forward_device(x, y, stream=st), 10, st)
+    out({"config": "intt", "workload": "2^%d-point GF(2^128) inverse additive NTT (r=0, coset 0)" % log_h,
+         "value": n / (ms_inv * 1e-3), "unit": "elements/s", "ms": ms_inv, "ms_forward_variant1": ms_fwd1,
+         "ms_forward_default": ms_fwd, "forward_default_variant": default,
+         "inverse_over_forward_variant1": ms_inv / ms_fwd1,
+         "hbm_gbps_algorithmic": 32.0 * n / (ms_inv * 1e-3) / 1e9})
 
 
 def c4(dev, out, nvars, ds):
@@ -314,6 +339,9 @@ def main():
         bb_line(dev, out, 20, 16)
     if "qm" in only:
         qm_line(dev, out, 24)
+    if "intt" in only:
+        intt_line(dev, out, 20)
+        intt_line(dev, out, 24)
     if a.out:
         with open(a.out, "w") as f:
             for d in lines:
