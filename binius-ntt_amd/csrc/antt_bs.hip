@@ -22,8 +22,13 @@
 //   (workgroup) index bit and every coset bit, so a twiddle is a handful of masked XORs.
 //
 // Stage schedule: block-bit stages go through LDS (partners change every stage). In the bottom
-// pass the 5 stages on index bits 0..4 pair bit-lanes of one word, so each thread keeps its two
-// blocks in registers for all of them and transposes them back to compact form in registers.
+// pass the 5 stages on index bits 0..4 pair bit-lanes of one word. A lane owns the same two blocks
+// (lane and lane + 64) for all of them and runs them as block stages on a packed pair: one delta
+// swap at distance 16 on entry makes word X the elements with index bit 4 clear and Y those with
+// it set, stage s is the block-stage butterfly on (X, Y), and a delta swap at distance 2^(s-1)
+// on the way back to LDS moves index bit s-1 out of the bit-lane number for the next stage. The
+// layout is never restored: the host tabulates the twiddle words for the rotated bit-lane meaning
+// (BsPass::pat2), and after stage 0 the transposed pair is written straight to its compact slots.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,10 +60,15 @@ struct BsParams {
 #ifdef BN_DEV
 #define BS_DBG(P) ((P).dbg)
 #define BS_TRACE(P) ((P).trace != nullptr)
+// the two-pass bottom kernel runs its in-word stages packed unless a development switch (flag 16,
+// a stop stage) asks for something else: then it takes the per-stage path of the single-pass kernel
+#define BS_PACKED(P) (!((P).dbg & 16) && (P).p.stop_j == 0)
 #else
 #define BS_DBG(P) 0
 #define BS_TRACE(P) false
+#define BS_PACKED(P) true
 #endif
+static_assert(sizeof(BsParams) <= 4096, "BsParams is a kernel argument");
 
 // One pass over every tile. Without PF a workgroup transforms tile blockIdx.x. With PF the grid
 // is persistent (workgroup b takes tiles b, b + grid, ...) and the next tile's global loads are
@@ -108,18 +118,23 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 	};
 	uint4 gbuf[kLoads];
 	auto issue = [&](const uint32_t* s, size_t ooff) {
+		// bottom pass: bb[m] = 5 + m (bs_prepare checks it), the tile is one contiguous run of
+		// 2^12 elements at ooff: a workgroup-uniform base and a 32-bit offset per lane
+		const uint32_t* const s0 = s + ooff * L;
 #pragma unroll
 		for (int r = 0; r < kLoads; r++) {
 			if (IN_COMPACT) {
 				// compact elements: 16-byte loads, 8*L lanes per 32-element block
 				const int u = tid + r * NT;
 				const int q = u / (8 * L), j = u % (8 * L);
-				gbuf[r] = (BS_DBG(P) & 1) ? make_uint4(u, j, q, tid) : ld_stream(s + (ooff | tile_off(q)) * L + 4 * j);
+				const uint32_t* g = LAST ? s0 + (uint32_t)(4 * u) : s + (ooff | tile_off(q)) * L + 4 * j;
+				gbuf[r] = (BS_DBG(P) & 1) ? make_uint4(u, j, q, tid) : ld_stream(g);
 			} else {
 				// bitsliced: limb l of block q is 128 contiguous bytes, each wave loads its own plane
 				const int u = lane + r * 64;
 				const int q = u >> 3, j = u & 7;
-				gbuf[r] = (BS_DBG(P) & 1) ? make_uint4(u, j, q, tid) : ld_stream(s + (ooff | tile_off(q)) * L + 32 * l + 4 * j);
+				const uint32_t* g = LAST ? s0 + (uint32_t)(q * 32 * L + 32 * l + 4 * j) : s + (ooff | tile_off(q)) * L + 32 * l + 4 * j;
+				gbuf[r] = (BS_DBG(P) & 1) ? make_uint4(u, j, q, tid) : ld_stream(g);
 			}
 		}
 	};
@@ -133,9 +148,16 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 
 	// ---- tile-bit stages (index bits >= 5), high to low. Lane = block pair of the wave's limb;
 	// only V and the twiddle are live during the multiply, U is read afterwards.
-	auto block_stage = [&](int j, int pair) {
-		unsigned long long t_a = TR ? ts() : 0;
-		const int m = ps.stage_m[j];
+	// In the bottom pass of a transform of two and more passes the same code runs stages 4..0
+	// (index bits inside the word, `inw`) on the
+	// packed pair (X, Y) that the lane keeps in the slots of blocks lane and lane + 64 (see
+	// pack_pair below): X is U, Y is V, the bit-lane part of the twiddle words comes from
+	// BsPass::pat2, and the delta swap for the next stage is applied on the way back to LDS.
+	auto block_stage = [&](int j, int pair, bool inw) {
+		// the pre / mul / post stamps (tr[5..7]) split the block-stage phase tr[1]: not the in-word stages
+		const bool TRB = TR && !inw;
+		unsigned long long t_a = TRB ? ts() : 0;
+		const int m = inw ? kBlkBits - 1 : ps.stage_m[j];
 		const int qu = ((pair >> m) << (m + 1)) | (pair & ((1 << m) - 1));
 		const int qv = qu | (1 << m);
 		const uint32_t w = cu_w[j] ^ tile_tw(j, qu);
@@ -152,7 +174,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 		// the stage on the top tile bit: qu's bits 0..5 are the lane's, and when none of them moves
 		// the twiddle (twt[j][0..5] = 0: the tile's other bits are lower stages) it is the
 		// workgroup-uniform part alone, so the circuit's twiddle side is scalar (bsm5_mul_w)
-		bool uni = FMAX == 32 && m == kBlkBits - 1 && ps.field[j] == 32 && !(BS_DBG(P) & 4);
+		bool uni = FMAX == 32 && !inw && m == kBlkBits - 1 && ps.field[j] == 32 && !(BS_DBG(P) & 4);
 #pragma unroll
 		for (int mm = 0; mm < kBlkBits - 1; mm++) uni = uni && ps.twt[j][mm] == 0u;
 		if (uni) {
@@ -161,9 +183,14 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 			bsm5_mul_w(V, (uint32_t)__builtin_amdgcn_readfirstlane((int)cu_w[j]), Pr);
 			__builtin_amdgcn_sched_barrier(0);
 		} else {
+		if (inw) {  // the bottom pass starts at stage 0: j is the stage
 #pragma unroll
-		for (int i = 0; i < 32; i++) W[i] = (uint32_t)__builtin_amdgcn_sbfe(w, i, 1);
-		if (TR) {
+			for (int i = 0; i < 32; i++) W[i] = ps.pat2[j][i] ^ (uint32_t)__builtin_amdgcn_sbfe(w, i, 1);
+		} else {
+#pragma unroll
+			for (int i = 0; i < 32; i++) W[i] = (uint32_t)__builtin_amdgcn_sbfe(w, i, 1);
+		}
+		if (TRB) {
 			const unsigned long long t = ts();
 			tr[5] += t - t_a;
 			t_a = t;
@@ -180,7 +207,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 			__builtin_amdgcn_sched_barrier(0);
 		}
 		}
-		if (TR) {
+		if (TRB) {
 			uint32_t acc = 0;
 #pragma unroll
 			for (int i = 0; i < 32; i++) acc ^= Pr[i];
@@ -189,17 +216,59 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 			tr[6] += t - t_a;
 			t_a = t;
 		}
+		if (inw && j > 0) {
+			// butterfly, then the delta swap at distance 2^(j-1): X' = index bit j-1 clear, Y' = set,
+			// and bit-lane bit j-1 becomes index bit j (shift count and lane mask as VGPR operands: an
+			// SGPR operand halves the issue rate)
+			const uint32_t d = vgpr(1u << (j - 1));
+			const uint32_t um = vgpr(~lane_mask(j - 1));
+#pragma unroll
+			for (int i = 0; i < 32; i += 4) {
+				uint32_t Uw[4], X[4], Y[4];
+				*(uint4*)Uw = FMAX <= 8 ? *(const uint4*)(U + i) : *(const uint4*)(pu + i);
+#pragma unroll
+				for (int t = 0; t < 4; t++) {
+					const uint32_t x = Uw[t] ^ Pr[i + t], y = V[i + t] ^ x;
+					X[t] = __builtin_amdgcn_bitop3_b32(x, y << d, um, 0xe4);  // (x & um) | (y << d & ~um)
+					Y[t] = __builtin_amdgcn_bitop3_b32(x >> d, y, um, 0xe4);  // (x >> d & um) | (y & ~um)
+				}
+				*(uint4*)(pu + i) = *(const uint4*)X;
+				*(uint4*)(pv + i) = *(const uint4*)Y;
+			}
+		} else {
+#pragma unroll
+			for (int i = 0; i < 32; i += 4) {
+				uint4 u = FMAX <= 8 ? *(const uint4*)(U + i) : *(const uint4*)(pu + i);
+				u.x ^= Pr[i];
+				u.y ^= Pr[i + 1];
+				u.z ^= Pr[i + 2];
+				u.w ^= Pr[i + 3];
+				*(uint4*)(pu + i) = u;
+				*(uint4*)(pv + i) = make_uint4(V[i] ^ u.x, V[i + 1] ^ u.y, V[i + 2] ^ u.z, V[i + 3] ^ u.w);
+			}
+		}
+		if (TRB) tr[7] += ts() - t_a;
+	};
+	// Entry to the in-word stages (bottom pass). A lane owns blocks A = lane and B = lane + 64,
+	// which differ in index bit 11. One delta swap at distance 16 makes X (A's slot) the elements
+	// with index bit 4 clear and Y (B's slot) those with it set; bit-lane bit 4 is index bit 11
+	// from here on. The stages never return to the canonical layout: at stage s bit-lane bits
+	// 0..s-1 are index bits 0..s-1 and bit-lane bits s..3 index bits s+1..4.
+	auto pack_pair = [&](uint32_t* pa, uint32_t* pb) {
+		const uint32_t d = vgpr(16u), um = vgpr(~lane_mask(4));
 #pragma unroll
 		for (int i = 0; i < 32; i += 4) {
-			uint4 u = FMAX <= 8 ? *(const uint4*)(U + i) : *(const uint4*)(pu + i);
-			u.x ^= Pr[i];
-			u.y ^= Pr[i + 1];
-			u.z ^= Pr[i + 2];
-			u.w ^= Pr[i + 3];
-			*(uint4*)(pu + i) = u;
-			*(uint4*)(pv + i) = make_uint4(V[i] ^ u.x, V[i + 1] ^ u.y, V[i + 2] ^ u.z, V[i + 3] ^ u.w);
+			uint32_t A[4], Bv[4], X[4], Y[4];
+			*(uint4*)A = *(const uint4*)(pa + i);
+			*(uint4*)Bv = *(const uint4*)(pb + i);
+#pragma unroll
+			for (int t = 0; t < 4; t++) {
+				X[t] = __builtin_amdgcn_bitop3_b32(A[t], Bv[t] << d, um, 0xe4);
+				Y[t] = __builtin_amdgcn_bitop3_b32(A[t] >> d, Bv[t], um, 0xe4);
+			}
+			*(uint4*)(pa + i) = *(const uint4*)X;
+			*(uint4*)(pb + i) = *(const uint4*)Y;
 		}
-		if (TR) tr[7] += ts() - t_a;
 	};
 
 	size_t tile = tile0;
@@ -270,83 +339,111 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 			tr[0] += t1 - t0;
 		}
 
-		const int jlow = max(LAST ? 5 : 0, ps.stop_j);
+		// The bottom pass of a transform of two and more passes runs stages 4..0 packed. The
+		// single-pass kernel keeps the per-stage pack / multiply / unpack path below: with the packed
+		// stages in its loop it spills 28 (L = 4) and 23 (L = 1) VGPRs against 9 and 5
+		const bool packed = ROLE == ROLE_LAST && BS_PACKED(P);
+		const int qa = lane, qb = qa | (kTileBlocks / 2);
+		uint32_t* pa = plane + qa * kLimbStride;
+		uint32_t* pb = plane + qb * kLimbStride;
+		const int jlow = packed ? 0 : max(LAST ? 5 : 0, ps.stop_j);
 		for (int j = ps.k - 1; j >= jlow; j--) {
-			if (!(BS_DBG(P) & 32)) block_stage(j, lane);
+			const bool inw = packed && j < 5;
+			if (packed && j == 4) {
+				if (TR) {
+					const unsigned long long t = ts();
+					tr[1] += t - t1;
+					t1 = t;
+				}
+				pack_pair(pa, pb);
+			}
+			if (inw || !(BS_DBG(P) & 32)) block_stage(j, lane, inw);
 			if (BS_DBG(P) & 64)
 				asm volatile("" ::: "memory");  // experiment: rely on in-order LDS execution only
 			else
 				wave_lds_sync();
 		}
-		if (TR) {
+		if (TR && !packed) {
 			const unsigned long long t = ts();
 			tr[1] += t - t1;
 			t1 = t;
 		}
 
 		if (LAST) {
-			// ---- stages 4..0 (index bits inside the word), lane-private: lane owns blocks qa = lane
-			// and qb = lane + 64 for all of them. Per stage both blocks share one multiply: A's
-			// v-lanes move down onto the u positions, B's v-lanes stay on the v positions (a pair's
-			// twiddle depends only on index bits above s).
-			const int qa = lane, qb = qa | (kTileBlocks / 2);
-			uint32_t* pa = plane + qa * kLimbStride;
-			uint32_t* pb = plane + qb * kLimbStride;
-			for (int s = 4; s >= ((BS_DBG(P) & 16) ? 5 : ps.stop_j); s--) {  // bottom pass starts at stage 0: j == s
-				// shift count and lane mask as VGPR operands (an SGPR operand halves the issue rate)
-				const uint32_t d = vgpr(1u << s);
-				const uint32_t um = vgpr(~lane_mask(s));  // u-lanes (bit s clear)
-				const uint32_t cb = cu_w[s] ^ tile_tw(s, qb);
-				uint32_t W[32], T[32];
+			// ---- back to compact words (lane-private)
+			if (packed) {
+				// after stage 0 bit-lane r of X is element 2 (r & 15) of block A (r < 16) or B, and of
+				// Y the element after it: pairs go straight to their slots
+				uint32_t X[32], Y[32];
 #pragma unroll
-				for (int i = 0; i < 32; i += 4) {
-					const uint4 a = *(const uint4*)(pa + i), b = *(const uint4*)(pb + i);
-					T[i] = __builtin_amdgcn_bitop3_b32(a.x >> d, b.x, um, 0xe4);  // (a>>d & um) | (b & ~um)
-					T[i + 1] = __builtin_amdgcn_bitop3_b32(a.y >> d, b.y, um, 0xe4);
-					T[i + 2] = __builtin_amdgcn_bitop3_b32(a.z >> d, b.z, um, 0xe4);
-					T[i + 3] = __builtin_amdgcn_bitop3_b32(a.w >> d, b.w, um, 0xe4);
-				}
-				// twiddle word i: pattern (bit-lane bits s+1..4) ^ block part, cb on B's lanes and
-				// ca = cb ^ twt[s][6] on A's (um) lanes; the host folds the um & twt[s][6] part into pat
+				for (int i = 0; i < 32; i += 4) *(uint4*)(X + i) = *(const uint4*)(pa + i);
 #pragma unroll
-				for (int i = 0; i < 32; i++) W[i] = ps.pat[s][i] ^ (uint32_t)__builtin_amdgcn_sbfe(cb, i, 1);
-				if (BS_DBG(P) & 4) {
+				for (int i = 0; i < 32; i += 4) *(uint4*)(Y + i) = *(const uint4*)(pb + i);
+				transpose32(X);
+				transpose32(Y);
 #pragma unroll
-					for (int i = 0; i < 32; i++) T[i] ^= W[i];
-				} else {
-					asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // operands complete (see block_stage)
-					__builtin_amdgcn_sched_barrier(0);
-					mul_tw<FMAX>(ps.field[s], T, W, T);
-					__builtin_amdgcn_sched_barrier(0);
-				}
+				for (int r = 0; r < 32; r += 2)
+					*(uint4*)((r & 16 ? pb : pa) + 2 * (r & 15)) = make_uint4(X[r], Y[r], X[r + 1], Y[r + 1]);
+			} else {
+				// per-stage path: both blocks share one multiply. A's v-lanes move down onto the u
+				// positions, B's v-lanes stay on the v positions (a pair's twiddle depends only on
+				// index bits above s), and the product is scattered back into A and B
+				for (int s = 4; s >= ((BS_DBG(P) & 16) ? 5 : ps.stop_j); s--) {  // bottom pass starts at stage 0: j == s
+					// shift count and lane mask as VGPR operands (an SGPR operand halves the issue rate)
+					const uint32_t d = vgpr(1u << s);
+					const uint32_t um = vgpr(~lane_mask(s));  // u-lanes (bit s clear)
+					const uint32_t cb = cu_w[s] ^ tile_tw(s, qb);
+					uint32_t W[32], T[32];
 #pragma unroll
-				for (int i = 0; i < 32; i += 4) {
-					uint32_t A[4], Bv[4];
-					*(uint4*)A = *(const uint4*)(pa + i);
-					*(uint4*)Bv = *(const uint4*)(pb + i);
-#pragma unroll
-					for (int t = 0; t < 4; t++) {
-						// u ^= w*v on the u-lanes, then v ^= u: (x & um) << d == (x << d) & ~um and
-						// (x & ~um) >> d == (x >> d) & um for these lane masks
-						const uint32_t a = __builtin_amdgcn_bitop3_b32(T[i + t], um, A[t], 0x6a);         // A ^ (T & um)
-						const uint32_t b = __builtin_amdgcn_bitop3_b32(T[i + t] >> d, um, Bv[t], 0x6a);  // B ^ ((T >> d) & um)
-						A[t] = __builtin_amdgcn_bitop3_b32(a << d, um, a, 0x9a);                          // a ^ ((a << d) & ~um)
-						Bv[t] = __builtin_amdgcn_bitop3_b32(b << d, um, b, 0x9a);
+					for (int i = 0; i < 32; i += 4) {
+						const uint4 a = *(const uint4*)(pa + i), b = *(const uint4*)(pb + i);
+						T[i] = __builtin_amdgcn_bitop3_b32(a.x >> d, b.x, um, 0xe4);  // (a>>d & um) | (b & ~um)
+						T[i + 1] = __builtin_amdgcn_bitop3_b32(a.y >> d, b.y, um, 0xe4);
+						T[i + 2] = __builtin_amdgcn_bitop3_b32(a.z >> d, b.z, um, 0xe4);
+						T[i + 3] = __builtin_amdgcn_bitop3_b32(a.w >> d, b.w, um, 0xe4);
 					}
-					*(uint4*)(pa + i) = *(const uint4*)A;
-					*(uint4*)(pb + i) = *(const uint4*)Bv;
+					// twiddle word i: pattern (bit-lane bits s+1..4) ^ block part, cb on B's lanes and
+					// ca = cb ^ twt[s][6] on A's (um) lanes; the host folds the um & twt[s][6] part into pat
+#pragma unroll
+					for (int i = 0; i < 32; i++) W[i] = ps.pat[s][i] ^ (uint32_t)__builtin_amdgcn_sbfe(cb, i, 1);
+					if (BS_DBG(P) & 4) {
+#pragma unroll
+						for (int i = 0; i < 32; i++) T[i] ^= W[i];
+					} else {
+						asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // operands complete (see block_stage)
+						__builtin_amdgcn_sched_barrier(0);
+						mul_tw<FMAX>(ps.field[s], T, W, T);
+						__builtin_amdgcn_sched_barrier(0);
+					}
+#pragma unroll
+					for (int i = 0; i < 32; i += 4) {
+						uint32_t A[4], Bv[4];
+						*(uint4*)A = *(const uint4*)(pa + i);
+						*(uint4*)Bv = *(const uint4*)(pb + i);
+#pragma unroll
+						for (int t = 0; t < 4; t++) {
+							// u ^= w*v on the u-lanes, then v ^= u: (x & um) << d == (x << d) & ~um and
+							// (x & ~um) >> d == (x >> d) & um for these lane masks
+							const uint32_t a = __builtin_amdgcn_bitop3_b32(T[i + t], um, A[t], 0x6a);         // A ^ (T & um)
+							const uint32_t b = __builtin_amdgcn_bitop3_b32(T[i + t] >> d, um, Bv[t], 0x6a);  // B ^ ((T >> d) & um)
+							A[t] = __builtin_amdgcn_bitop3_b32(a << d, um, a, 0x9a);                          // a ^ ((a << d) & ~um)
+							Bv[t] = __builtin_amdgcn_bitop3_b32(b << d, um, b, 0x9a);
+						}
+						*(uint4*)(pa + i) = *(const uint4*)A;
+						*(uint4*)(pb + i) = *(const uint4*)Bv;
+					}
 				}
-			}
-			// back to compact words (lane-private)
+				// canonical blocks back to compact words
 #pragma unroll
-			for (int h = 0; h < 2; h++) {
-				uint32_t* x = h ? pb : pa;
-				uint32_t r[32];
+				for (int h = 0; h < 2; h++) {
+					uint32_t* x = h ? pb : pa;
+					uint32_t r[32];
 #pragma unroll
-				for (int i = 0; i < 32; i += 4) *(uint4*)(r + i) = *(const uint4*)(x + i);
-				transpose32(r);
+					for (int i = 0; i < 32; i += 4) *(uint4*)(r + i) = *(const uint4*)(x + i);
+					transpose32(r);
 #pragma unroll
-				for (int i = 0; i < 32; i += 4) *(uint4*)(x + i) = *(const uint4*)(r + i);
+					for (int i = 0; i < 32; i += 4) *(uint4*)(x + i) = *(const uint4*)(r + i);
+				}
 			}
 			if (TR) {
 				const unsigned long long t = ts();
@@ -358,15 +455,24 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 		// ---- store tile
 		if (LAST) {
 			__syncthreads();  // compact elements gather one word from every limb plane
-			for (int u = tid; u < kTileBlocks * 8 * L; u += NT) {
-				const int q = u / (8 * L), j = u % (8 * L);
+			// the tile is one contiguous run (see issue()): thread u of iteration it writes 16 bytes at
+			// word 4 (u + it NT), and gathers them 8 blocks further on in LDS each time
+			uint32_t* const g0 = dst + outer_off * L;
+			const int q0 = tid / (8 * L), j0 = tid % (8 * L);
+			const uint32_t* sp[4];
+#pragma unroll
+			for (int t = 0; t < 4; t++) {
+				const int word = 4 * j0 + t;
+				sp[t] = lds + (word % L) * kPlane + q0 * kLimbStride + word / L;
+			}
+			constexpr int kStoreIters = kTileBlocks * 8 * L / NT;  // 16
+			constexpr int kStepBlocks = NT / (8 * L);              // 8
+#pragma unroll
+			for (int it = 0; it < kStoreIters; it++) {
 				uint32_t w[4];
 #pragma unroll
-				for (int t = 0; t < 4; t++) {
-					const int word = 4 * j + t;
-					w[t] = lds[(word % L) * kPlane + q * kLimbStride + word / L];
-				}
-				if (!(BS_DBG(P) & 2)) st_stream(dst + (outer_off | tile_off(q)) * L + 4 * j, make_uint4(w[0], w[1], w[2], w[3]));
+				for (int t = 0; t < 4; t++) w[t] = sp[t][it * kStepBlocks * kLimbStride];
+				if (!(BS_DBG(P) & 2)) st_stream(g0 + (uint32_t)(4 * (tid + it * NT)), make_uint4(w[0], w[1], w[2], w[3]));
 			}
 		} else {
 #pragma unroll 4
@@ -760,6 +866,15 @@ static std::vector<BsPass> plan_passes(const bn_antt_plan* plan) {
 					if ((p.twt[j][kBlkBits - 1] >> i) & 1) w ^= ~lane_mask(s);
 					p.pat[s][i] = w;
 				}
+				// packed in-word stages (antt_bs_pass): the stages above s have rotated index bit b
+				// onto bit-lane bit b - 1, and bit-lane bit 4 is the tile's top block bit
+				for (int i = 0; i < 32; i++) {
+					uint32_t w = 0;
+					for (int b = s + 1; b < 5; b++)
+						if ((S(s, b - s - 1) >> i) & 1) w ^= lane_mask(b - 1);
+					if ((p.twt[j][kBlkBits - 1] >> i) & 1) w ^= lane_mask(4);
+					p.pat2[s][i] = w;
+				}
 			}
 		}
 		return p;
@@ -838,6 +953,13 @@ static const void* split_kernel_for(int role) {
 	}
 }
 
+// plan_passes gives the bottom pass the tile bits bb[m] = 5 + m; its kernels rely on it
+static bool bottom_tile_contiguous(const BsPass& p) {
+	for (int m = 0; m < kBlkBits; m++)
+		if (p.bb[m] != 5 + m) return false;
+	return true;
+}
+
 int pass_fmax(const BsPass& p) {
 	int f = 8;
 	for (int j = 0; j < p.k; j++) f = std::max(f, p.field[j]);
@@ -865,6 +987,12 @@ int bs_prepare(bn_antt_plan* plan) {
 		for (int f1 : {8, 32})
 			BN_HIP(hipFuncSetAttribute(persist3_kernel(f0, f1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(4)));
 #endif
+	// the pass tables are built here, once per plan, so that a bottom pass whose tile is not the
+	// contiguous run its kernels address fails the plan and never reaches a launch
+	size_t n_passes = 0;
+	const BsPass* passes = bs_passes(plan, &n_passes);
+	if (n_passes == 0 || !bottom_tile_contiguous(passes[n_passes - 1]))
+		BN_FAIL(BN_ERR_UNSUPPORTED, "bottom pass: tile block bits are not index bits 5..11");
 	int rc = rr_prepare(plan);
 	if (rc != BN_OK) return rc;
 	int cus = 0;
@@ -884,6 +1012,44 @@ const BsPass* bs_passes(bn_antt_plan* plan, size_t* n_passes) {
 	*n_passes = plan->bs_passes.size() / sizeof(BsPass);
 	return (const BsPass*)plan->bs_passes.data();
 }
+
+}  // namespace bn
+
+// Host only (no plan, no device): the bottom pass's in-word twiddle tables, for checking them
+// against an independent twiddle computation. Layout: see include/binius_ntt_amd.h.
+extern "C" int bn_antt_inword_tables(int log_h, int log_rate, uint32_t* out, size_t out_words) {
+	using namespace bn;
+	constexpr size_t kStageWords = 32 + kBlkBits + kMaxOuter + kMaxRateBits + 1;
+	constexpr size_t kWords = 4 + 1 + kMaxOuter + 5 * kStageWords;
+	BN_CHECK_ARG(out != nullptr, "output pointer is NULL");
+	BN_CHECK_ARG(log_rate >= 0 && log_rate <= 4 && log_h + log_rate <= 32, "log_h + log_rate must be <= 32, log_rate in [0,4]");
+	BN_CHECK_ARG(out_words >= kWords, "output holds %zu words, need %zu", out_words, kWords);
+	bn_antt_plan plan;
+	plan.log_h = log_h;
+	plan.log_rate = log_rate;
+	plan.width = log_h + log_rate - 1;
+	if (!bs_supports(&plan)) BN_FAIL(BN_ERR_UNSUPPORTED, "the bitsliced passes need log_h >= %d", kMinLogH);
+	subspace_evals(log_h, log_rate, plan.s_host);
+	const BsPass p = plan_passes(&plan).back();
+	if (!bottom_tile_contiguous(p)) BN_FAIL(BN_ERR_UNSUPPORTED, "bottom pass: tile block bits are not index bits 5..11");
+	uint32_t* o = out;
+	*o++ = (uint32_t)kWords;
+	*o++ = (uint32_t)kBlkBits;
+	*o++ = (uint32_t)kMaxOuter;
+	*o++ = (uint32_t)kMaxRateBits;
+	*o++ = (uint32_t)p.n_outer;
+	for (int m = 0; m < kMaxOuter; m++) *o++ = (uint32_t)p.ob[m];
+	for (int s = 0; s < 5; s++) {
+		for (int i = 0; i < 32; i++) *o++ = p.pat2[s][i];
+		for (int m = 0; m < kBlkBits; m++) *o++ = p.twt[s][m];
+		for (int m = 0; m < kMaxOuter; m++) *o++ = p.two[s][m];
+		for (int c = 0; c < kMaxRateBits; c++) *o++ = p.twc[s][c];
+		*o++ = (uint32_t)p.field[s];
+	}
+	return BN_OK;
+}
+
+namespace bn {
 
 struct BsDevKnobs {
 	int pf_mode = 0, dbg = 0, stop_stage = -1, split = -1, mid_pf = -1, rr_last = -1;

@@ -30,6 +30,9 @@ struct BsPass {
 	uint32_t two[kMaxStages][kMaxOuter];     // ... of outer bit m
 	uint32_t twc[kMaxStages][kMaxRateBits];  // ... of coset bit c
 	uint32_t pat[5][32];                     // stages 0..4: bit-lane part of the twiddle words
+	// the same for antt_bs_pass's packed in-word stages (bottom pass): at stage s bit-lane bits
+	// s..3 are index bits s+1..4 and bit-lane bit 4 is the tile's top block bit
+	uint32_t pat2[5][32];
 };
 
 // Register-tile pass table (variant 4): wave w owns limb plane w of the tile; lane L holds two

@@ -114,6 +114,23 @@ int bn_antt_time_passes(bn_antt_plan* plan, const void* d_in, void* d_out, size_
  * false>(bn::BsParams)"), so committed counter summaries can be matched to the launches exactly.
  * BN_ERR_UNSUPPORTED for variant 0. */
 int bn_antt_pass_kernel_name(bn_antt_plan* plan, int pass, char* buf, size_t cap);
+/* Test hook (no reference counterpart; host only: no plan, no device): the twiddle tables of the
+ * in-word stages 0..4 of the bitsliced bottom pass (variants 1 and 5) of a (log_h, log_rate)
+ * transform, log_h >= 12, so that a test can rebuild every twiddle from them. The first four
+ * words give the layout, so a caller hard-codes none of it (a 1024-word buffer is ample):
+ *   words, B, O, R                   words written in all; block bits per tile (7), table rows
+ *                                    for fixed bits (20) and for coset bits (8)
+ *   n_outer, ob[O]                   the index bits (>= 12) fixed per tile, ascending
+ *   then for s = 0..4, 32 + B + O + R + 1 words:
+ *     pat2[32]  word i = bit i of the bit-lane part of the twiddle: at stage s bit-lane bits
+ *               0..s-1 are index bits 0..s-1 (no twiddle part), bit-lane bits s..3 index bits
+ *               s+1..4 and bit-lane bit 4 index bit 11
+ *     twt[B]    contribution of index bit 5 + m (the lane owns bits 5..10; bit 11 is in pat2)
+ *     two[O]    contribution of fixed index bit ob[m]
+ *     twc[R]    contribution of coset bit c
+ *     field     8/16/32: the sub-field holding every twiddle of the stage
+ * BN_ERR_UNSUPPORTED for log_h < 12, BN_ERR_INVALID if out_words is too small. */
+int bn_antt_inword_tables(int log_h, int log_rate, uint32_t* out, size_t out_words);
 
 /* ------------------------------------------------------------------------------------
  * Binary tower field arithmetic (src/ulvt/finite_fields/)
