@@ -47,12 +47,9 @@ namespace bn {
 struct BsParams {
 	const uint32_t* src;
 	uint32_t* dst;
-	size_t ntiles;  // tiles of the pass; the (persistent) grid may be smaller
 	int log_h, log_rate;
 	unsigned long long* trace;  // BN_TRACE=1: per-wave phase timestamps (dev tool)
-	int dbg;  // timing experiments only (BN_DEBUG_FLAGS): 1 no loads, 2 no stores, 4 no multiplies,
-	          // 8 no stage barriers, 16 no in-word stages, 32 no tile-bit stages,
-	          // 64 no lgkmcnt wait between stages
+	int dbg;  // timing experiments only (BN_DEBUG_FLAGS): 1 no loads, 2 no stores, 4 no multiplies
 	BsPass p;
 };
 
@@ -60,26 +57,23 @@ struct BsParams {
 #ifdef BN_DEV
 #define BS_DBG(P) ((P).dbg)
 #define BS_TRACE(P) ((P).trace != nullptr)
-// the two-pass bottom kernel runs its in-word stages packed unless a development switch (flag 16,
-// a stop stage) asks for something else: then it takes the per-stage path of the single-pass kernel
-#define BS_PACKED(P) (!((P).dbg & 16) && (P).p.stop_j == 0)
 #else
 #define BS_DBG(P) 0
 #define BS_TRACE(P) false
-#define BS_PACKED(P) true
 #endif
 static_assert(sizeof(BsParams) <= 4096, "BsParams is a kernel argument");
 
-// One pass over every tile. Without PF a workgroup transforms tile blockIdx.x. With PF the grid
-// is persistent (workgroup b takes tiles b, b + grid, ...) and the next tile's global loads are
-// issued into registers right after the current tile reaches LDS, so they are in flight during
-// the stages instead of exposed at the start of the next tile.
-template <int L, int ROLE, int FMAX, bool PF>
-__device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
+// One pass over every tile: workgroup b transforms tile b.
+template <int L, int ROLE, int FMAX>
+__device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 	extern __shared__ uint32_t lds[];
 	constexpr int NT = 64 * L;
 	constexpr bool IN_COMPACT = ROLE == ROLE_FIRST || ROLE == ROLE_SINGLE;
 	constexpr bool LAST = ROLE == ROLE_LAST || ROLE == ROLE_SINGLE;  // bottom pass, compact out
+	// The bottom pass of a transform of two and more passes runs stages 4..0 packed. The
+	// single-pass kernel keeps the per-stage pack / multiply / unpack path: with the packed
+	// stages in its loop it spills 28 (L = 4) and 23 (L = 1) VGPRs against 9 and 5
+	constexpr bool packed = ROLE == ROLE_LAST;
 	const BsPass& ps = P.p;
 	const int tid = threadIdx.x;
 	// wave w owns limb w of the tile for every stage: the waves never wait for each other
@@ -89,7 +83,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 	uint32_t* cu_w = lds + L * kPlane + l * kMaxStages;  // this wave's copy of the uniform twiddle parts
 	const size_t n = (size_t)1 << P.log_h;
 	const bool TR = BS_TRACE(P);
-	unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // load, block, in-word, store, tiles, pre, mul, post
+	unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // load, block, in-word, store, (wave-)tiles, pre, mul, post
 	auto ts = [&]() -> unsigned long long {
 		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 		return __builtin_amdgcn_s_memtime();
@@ -102,20 +96,16 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 		return off;
 	};
 	// tile -> (outer bits, coset, batch) -> addresses
-	size_t outer, outer_off;
-	int coset;
-	uint32_t* dst;
-	const uint32_t* src;
-	auto geo = [&](size_t t, size_t& o, size_t& ooff, int& c, uint32_t*& d, const uint32_t*& s) {
-		o = t & (((size_t)1 << ps.n_outer) - 1);
-		const size_t rest = t >> ps.n_outer;
-		c = (int)(rest & ((1u << P.log_rate) - 1));
-		const size_t batch = rest >> P.log_rate;
-		ooff = 0;
-		for (int m = 0; m < ps.n_outer; m++) ooff |= ((o >> m) & 1) << ps.ob[m];
-		d = P.dst + (((batch << P.log_rate) + (size_t)c) * n) * L;
-		s = IN_COMPACT ? (P.src + batch * n * L) : d;
-	};
+	const size_t tile = blockIdx.x;
+	const size_t outer = tile & (((size_t)1 << ps.n_outer) - 1);
+	const size_t rest = tile >> ps.n_outer;
+	const int coset = (int)(rest & ((1u << P.log_rate) - 1));
+	const size_t batch = rest >> P.log_rate;
+	size_t outer_off = 0;
+	for (int m = 0; m < ps.n_outer; m++) outer_off |= ((outer >> m) & 1) << ps.ob[m];
+	uint32_t* const dst = P.dst + (((batch << P.log_rate) + (size_t)coset) * n) * L;
+	const uint32_t* const src = IN_COMPACT ? (P.src + batch * n * L) : dst;
+	// the tile's global loads, all in flight at once
 	uint4 gbuf[kLoads];
 	auto issue = [&](const uint32_t* s, size_t ooff) {
 		// bottom pass: bb[m] = 5 + m (bs_prepare checks it), the tile is one contiguous run of
@@ -271,59 +261,150 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 		}
 	};
 
-	size_t tile = tile0;
-	geo(tile, outer, outer_off, coset, dst, src);
-	if (PF) issue(src, outer_off);
-	for (;;) {
-		unsigned long long t0 = TR ? ts() : 0;
-		// the previous tile's cross-plane LDS readers (compact store) / writers (compact load)
-		// are done before this tile's planes are overwritten
-		if (IN_COMPACT || LAST) __syncthreads();
-		if (!PF) issue(src, outer_off);
+	unsigned long long t0 = TR ? ts() : 0;
+	issue(src, outer_off);
 
-		// workgroup-uniform twiddle part of every stage (outer + coset bits), one lane per stage
-		if (lane < ps.k) {
-			uint32_t c = 0;
-			for (int m = 0; m < ps.n_outer; m++) c ^= ps.two[lane][m] & (0u - (uint32_t)((outer >> m) & 1));
-			for (int b = 0; b < P.log_rate; b++) c ^= ps.twc[lane][b] & (0u - (uint32_t)((coset >> b) & 1));
-			cu_w[lane] = c;
-		}
+	// workgroup-uniform twiddle part of every stage (outer + coset bits), one lane per stage
+	if (lane < ps.k) {
+		uint32_t c = 0;
+		for (int m = 0; m < ps.n_outer; m++) c ^= ps.two[lane][m] & (0u - (uint32_t)((outer >> m) & 1));
+		for (int b = 0; b < P.log_rate; b++) c ^= ps.twc[lane][b] & (0u - (uint32_t)((coset >> b) & 1));
+		cu_w[lane] = c;
+	}
 
-		// ---- tile into LDS
+	// ---- tile into LDS
 #pragma unroll
-		for (int r = 0; r < kLoads; r++) {
-			const uint4 g = gbuf[r];
-			if (IN_COMPACT) {
-				// split by limb into the planes
-				const int u = tid + r * NT;
-				const int q = u / (8 * L), j = u % (8 * L);
-				const uint32_t w[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-				for (int t = 0; t < 4; t++) {
-					const int word = 4 * j + t;
-					lds[(word % L) * kPlane + q * kLimbStride + word / L] = w[t];
-				}
-			} else {
-				const int u = lane + r * 64;
-				const int q = u >> 3, j = u & 7;
-				*(uint4*)(plane + q * kLimbStride + 4 * j) = g;
-			}
-		}
-		const size_t next = tile + gridDim.x;
-		const bool has_next = PF && next < P.ntiles;  // without PF: one tile per workgroup
-		size_t n_outer_v = outer, n_ooff = outer_off;
-		int n_coset = coset;
-		uint32_t* n_dst = dst;
-		const uint32_t* n_src = src;
-		if (has_next) {
-			geo(next, n_outer_v, n_ooff, n_coset, n_dst, n_src);
-			issue(n_src, n_ooff);  // in flight during this tile's stages
-		}
+	for (int r = 0; r < kLoads; r++) {
+		const uint4 g = gbuf[r];
 		if (IN_COMPACT) {
-			// per-(block, limb) 32x32 transposes of this wave's plane
-			__syncthreads();
-			for (int q = lane; q < kTileBlocks; q += 64) {
-				uint32_t* x = plane + q * kLimbStride;
+			// split by limb into the planes
+			const int u = tid + r * NT;
+			const int q = u / (8 * L), j = u % (8 * L);
+			const uint32_t w[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+			for (int t = 0; t < 4; t++) {
+				const int word = 4 * j + t;
+				lds[(word % L) * kPlane + q * kLimbStride + word / L] = w[t];
+			}
+		} else {
+			const int u = lane + r * 64;
+			const int q = u >> 3, j = u & 7;
+			*(uint4*)(plane + q * kLimbStride + 4 * j) = g;
+		}
+	}
+	if (IN_COMPACT) {
+		// per-(block, limb) 32x32 transposes of this wave's plane
+		__syncthreads();
+		for (int q = lane; q < kTileBlocks; q += 64) {
+			uint32_t* x = plane + q * kLimbStride;
+			uint32_t r[32];
+#pragma unroll
+			for (int i = 0; i < 32; i += 4) *(uint4*)(r + i) = *(const uint4*)(x + i);
+			transpose32(r);
+#pragma unroll
+			for (int i = 0; i < 32; i += 4) *(uint4*)(x + i) = *(const uint4*)(r + i);
+		}
+	}
+	wave_lds_sync();
+	unsigned long long t1 = 0;
+	if (TR) {
+		t1 = ts();
+		tr[0] += t1 - t0;
+	}
+
+	// the lane's two blocks of the in-word stages and of the transposes
+	const int qa = lane, qb = qa | (kTileBlocks / 2);
+	uint32_t* pa = plane + qa * kLimbStride;
+	uint32_t* pb = plane + qb * kLimbStride;
+	// the single-pass kernel stops above the in-word stages: it runs them per stage below
+	constexpr int jlow = ROLE == ROLE_SINGLE ? 5 : 0;
+	for (int j = ps.k - 1; j >= jlow; j--) {
+		const bool inw = packed && j < 5;
+		if (packed && j == 4) {
+			if (TR) {
+				const unsigned long long t = ts();
+				tr[1] += t - t1;
+				t1 = t;
+			}
+			pack_pair(pa, pb);
+		}
+		block_stage(j, lane, inw);
+		wave_lds_sync();
+	}
+	if (TR && !packed) {
+		const unsigned long long t = ts();
+		tr[1] += t - t1;
+		t1 = t;
+	}
+
+	if (LAST) {
+		// ---- back to compact words (lane-private)
+		if (packed) {
+			// after stage 0 bit-lane r of X is element 2 (r & 15) of block A (r < 16) or B, and of
+			// Y the element after it: pairs go straight to their slots
+			uint32_t X[32], Y[32];
+#pragma unroll
+			for (int i = 0; i < 32; i += 4) *(uint4*)(X + i) = *(const uint4*)(pa + i);
+#pragma unroll
+			for (int i = 0; i < 32; i += 4) *(uint4*)(Y + i) = *(const uint4*)(pb + i);
+			transpose32(X);
+			transpose32(Y);
+#pragma unroll
+			for (int r = 0; r < 32; r += 2)
+				*(uint4*)((r & 16 ? pb : pa) + 2 * (r & 15)) = make_uint4(X[r], Y[r], X[r + 1], Y[r + 1]);
+		} else {
+			// per-stage path: both blocks share one multiply. A's v-lanes move down onto the u
+			// positions, B's v-lanes stay on the v positions (a pair's twiddle depends only on
+			// index bits above s), and the product is scattered back into A and B
+			for (int s = 4; s >= 0; s--) {  // bottom pass starts at stage 0: j == s
+				// shift count and lane mask as VGPR operands (an SGPR operand halves the issue rate)
+				const uint32_t d = vgpr(1u << s);
+				const uint32_t um = vgpr(~lane_mask(s));  // u-lanes (bit s clear)
+				const uint32_t cb = cu_w[s] ^ tile_tw(s, qb);
+				uint32_t W[32], T[32];
+#pragma unroll
+				for (int i = 0; i < 32; i += 4) {
+					const uint4 a = *(const uint4*)(pa + i), b = *(const uint4*)(pb + i);
+					T[i] = __builtin_amdgcn_bitop3_b32(a.x >> d, b.x, um, 0xe4);  // (a>>d & um) | (b & ~um)
+					T[i + 1] = __builtin_amdgcn_bitop3_b32(a.y >> d, b.y, um, 0xe4);
+					T[i + 2] = __builtin_amdgcn_bitop3_b32(a.z >> d, b.z, um, 0xe4);
+					T[i + 3] = __builtin_amdgcn_bitop3_b32(a.w >> d, b.w, um, 0xe4);
+				}
+				// twiddle word i: pattern (bit-lane bits s+1..4) ^ block part, cb on B's lanes and
+				// ca = cb ^ twt[s][6] on A's (um) lanes; the host folds the um & twt[s][6] part into pat
+#pragma unroll
+				for (int i = 0; i < 32; i++) W[i] = ps.pat[s][i] ^ (uint32_t)__builtin_amdgcn_sbfe(cb, i, 1);
+				if (BS_DBG(P) & 4) {
+#pragma unroll
+					for (int i = 0; i < 32; i++) T[i] ^= W[i];
+				} else {
+					asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // operands complete (see block_stage)
+					__builtin_amdgcn_sched_barrier(0);
+					mul_tw<FMAX>(ps.field[s], T, W, T);
+					__builtin_amdgcn_sched_barrier(0);
+				}
+#pragma unroll
+				for (int i = 0; i < 32; i += 4) {
+					uint32_t A[4], Bv[4];
+					*(uint4*)A = *(const uint4*)(pa + i);
+					*(uint4*)Bv = *(const uint4*)(pb + i);
+#pragma unroll
+					for (int t = 0; t < 4; t++) {
+						// u ^= w*v on the u-lanes, then v ^= u: (x & um) << d == (x << d) & ~um and
+						// (x & ~um) >> d == (x >> d) & um for these lane masks
+						const uint32_t a = __builtin_amdgcn_bitop3_b32(T[i + t], um, A[t], 0x6a);         // A ^ (T & um)
+						const uint32_t b = __builtin_amdgcn_bitop3_b32(T[i + t] >> d, um, Bv[t], 0x6a);  // B ^ ((T >> d) & um)
+						A[t] = __builtin_amdgcn_bitop3_b32(a << d, um, a, 0x9a);                          // a ^ ((a << d) & ~um)
+						Bv[t] = __builtin_amdgcn_bitop3_b32(b << d, um, b, 0x9a);
+					}
+					*(uint4*)(pa + i) = *(const uint4*)A;
+					*(uint4*)(pb + i) = *(const uint4*)Bv;
+				}
+			}
+			// canonical blocks back to compact words
+#pragma unroll
+			for (int h = 0; h < 2; h++) {
+				uint32_t* x = h ? pb : pa;
 				uint32_t r[32];
 #pragma unroll
 				for (int i = 0; i < 32; i += 4) *(uint4*)(r + i) = *(const uint4*)(x + i);
@@ -332,168 +413,47 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 				for (int i = 0; i < 32; i += 4) *(uint4*)(x + i) = *(const uint4*)(r + i);
 			}
 		}
-		wave_lds_sync();
-		unsigned long long t1 = 0;
 		if (TR) {
-			t1 = ts();
-			tr[0] += t1 - t0;
-		}
-
-		// The bottom pass of a transform of two and more passes runs stages 4..0 packed. The
-		// single-pass kernel keeps the per-stage pack / multiply / unpack path below: with the packed
-		// stages in its loop it spills 28 (L = 4) and 23 (L = 1) VGPRs against 9 and 5
-		const bool packed = ROLE == ROLE_LAST && BS_PACKED(P);
-		const int qa = lane, qb = qa | (kTileBlocks / 2);
-		uint32_t* pa = plane + qa * kLimbStride;
-		uint32_t* pb = plane + qb * kLimbStride;
-		const int jlow = packed ? 0 : max(LAST ? 5 : 0, ps.stop_j);
-		for (int j = ps.k - 1; j >= jlow; j--) {
-			const bool inw = packed && j < 5;
-			if (packed && j == 4) {
-				if (TR) {
-					const unsigned long long t = ts();
-					tr[1] += t - t1;
-					t1 = t;
-				}
-				pack_pair(pa, pb);
-			}
-			if (inw || !(BS_DBG(P) & 32)) block_stage(j, lane, inw);
-			if (BS_DBG(P) & 64)
-				asm volatile("" ::: "memory");  // experiment: rely on in-order LDS execution only
-			else
-				wave_lds_sync();
-		}
-		if (TR && !packed) {
 			const unsigned long long t = ts();
-			tr[1] += t - t1;
+			tr[2] += t - t1;
 			t1 = t;
 		}
+	}
 
-		if (LAST) {
-			// ---- back to compact words (lane-private)
-			if (packed) {
-				// after stage 0 bit-lane r of X is element 2 (r & 15) of block A (r < 16) or B, and of
-				// Y the element after it: pairs go straight to their slots
-				uint32_t X[32], Y[32];
+	// ---- store tile
+	if (LAST) {
+		__syncthreads();  // compact elements gather one word from every limb plane
+		// the tile is one contiguous run (see issue()): thread u of iteration it writes 16 bytes at
+		// word 4 (u + it NT), and gathers them 8 blocks further on in LDS each time
+		uint32_t* const g0 = dst + outer_off * L;
+		const int q0 = tid / (8 * L), j0 = tid % (8 * L);
+		const uint32_t* sp[4];
 #pragma unroll
-				for (int i = 0; i < 32; i += 4) *(uint4*)(X + i) = *(const uint4*)(pa + i);
-#pragma unroll
-				for (int i = 0; i < 32; i += 4) *(uint4*)(Y + i) = *(const uint4*)(pb + i);
-				transpose32(X);
-				transpose32(Y);
-#pragma unroll
-				for (int r = 0; r < 32; r += 2)
-					*(uint4*)((r & 16 ? pb : pa) + 2 * (r & 15)) = make_uint4(X[r], Y[r], X[r + 1], Y[r + 1]);
-			} else {
-				// per-stage path: both blocks share one multiply. A's v-lanes move down onto the u
-				// positions, B's v-lanes stay on the v positions (a pair's twiddle depends only on
-				// index bits above s), and the product is scattered back into A and B
-				for (int s = 4; s >= ((BS_DBG(P) & 16) ? 5 : ps.stop_j); s--) {  // bottom pass starts at stage 0: j == s
-					// shift count and lane mask as VGPR operands (an SGPR operand halves the issue rate)
-					const uint32_t d = vgpr(1u << s);
-					const uint32_t um = vgpr(~lane_mask(s));  // u-lanes (bit s clear)
-					const uint32_t cb = cu_w[s] ^ tile_tw(s, qb);
-					uint32_t W[32], T[32];
-#pragma unroll
-					for (int i = 0; i < 32; i += 4) {
-						const uint4 a = *(const uint4*)(pa + i), b = *(const uint4*)(pb + i);
-						T[i] = __builtin_amdgcn_bitop3_b32(a.x >> d, b.x, um, 0xe4);  // (a>>d & um) | (b & ~um)
-						T[i + 1] = __builtin_amdgcn_bitop3_b32(a.y >> d, b.y, um, 0xe4);
-						T[i + 2] = __builtin_amdgcn_bitop3_b32(a.z >> d, b.z, um, 0xe4);
-						T[i + 3] = __builtin_amdgcn_bitop3_b32(a.w >> d, b.w, um, 0xe4);
-					}
-					// twiddle word i: pattern (bit-lane bits s+1..4) ^ block part, cb on B's lanes and
-					// ca = cb ^ twt[s][6] on A's (um) lanes; the host folds the um & twt[s][6] part into pat
-#pragma unroll
-					for (int i = 0; i < 32; i++) W[i] = ps.pat[s][i] ^ (uint32_t)__builtin_amdgcn_sbfe(cb, i, 1);
-					if (BS_DBG(P) & 4) {
-#pragma unroll
-						for (int i = 0; i < 32; i++) T[i] ^= W[i];
-					} else {
-						asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // operands complete (see block_stage)
-						__builtin_amdgcn_sched_barrier(0);
-						mul_tw<FMAX>(ps.field[s], T, W, T);
-						__builtin_amdgcn_sched_barrier(0);
-					}
-#pragma unroll
-					for (int i = 0; i < 32; i += 4) {
-						uint32_t A[4], Bv[4];
-						*(uint4*)A = *(const uint4*)(pa + i);
-						*(uint4*)Bv = *(const uint4*)(pb + i);
-#pragma unroll
-						for (int t = 0; t < 4; t++) {
-							// u ^= w*v on the u-lanes, then v ^= u: (x & um) << d == (x << d) & ~um and
-							// (x & ~um) >> d == (x >> d) & um for these lane masks
-							const uint32_t a = __builtin_amdgcn_bitop3_b32(T[i + t], um, A[t], 0x6a);         // A ^ (T & um)
-							const uint32_t b = __builtin_amdgcn_bitop3_b32(T[i + t] >> d, um, Bv[t], 0x6a);  // B ^ ((T >> d) & um)
-							A[t] = __builtin_amdgcn_bitop3_b32(a << d, um, a, 0x9a);                          // a ^ ((a << d) & ~um)
-							Bv[t] = __builtin_amdgcn_bitop3_b32(b << d, um, b, 0x9a);
-						}
-						*(uint4*)(pa + i) = *(const uint4*)A;
-						*(uint4*)(pb + i) = *(const uint4*)Bv;
-					}
-				}
-				// canonical blocks back to compact words
-#pragma unroll
-				for (int h = 0; h < 2; h++) {
-					uint32_t* x = h ? pb : pa;
-					uint32_t r[32];
-#pragma unroll
-					for (int i = 0; i < 32; i += 4) *(uint4*)(r + i) = *(const uint4*)(x + i);
-					transpose32(r);
-#pragma unroll
-					for (int i = 0; i < 32; i += 4) *(uint4*)(x + i) = *(const uint4*)(r + i);
-				}
-			}
-			if (TR) {
-				const unsigned long long t = ts();
-				tr[2] += t - t1;
-				t1 = t;
-			}
+		for (int t = 0; t < 4; t++) {
+			const int word = 4 * j0 + t;
+			sp[t] = lds + (word % L) * kPlane + q0 * kLimbStride + word / L;
 		}
-
-		// ---- store tile
-		if (LAST) {
-			__syncthreads();  // compact elements gather one word from every limb plane
-			// the tile is one contiguous run (see issue()): thread u of iteration it writes 16 bytes at
-			// word 4 (u + it NT), and gathers them 8 blocks further on in LDS each time
-			uint32_t* const g0 = dst + outer_off * L;
-			const int q0 = tid / (8 * L), j0 = tid % (8 * L);
-			const uint32_t* sp[4];
+		constexpr int kStoreIters = kTileBlocks * 8 * L / NT;  // 16
+		constexpr int kStepBlocks = NT / (8 * L);              // 8
 #pragma unroll
-			for (int t = 0; t < 4; t++) {
-				const int word = 4 * j0 + t;
-				sp[t] = lds + (word % L) * kPlane + q0 * kLimbStride + word / L;
-			}
-			constexpr int kStoreIters = kTileBlocks * 8 * L / NT;  // 16
-			constexpr int kStepBlocks = NT / (8 * L);              // 8
+		for (int it = 0; it < kStoreIters; it++) {
+			uint32_t w[4];
 #pragma unroll
-			for (int it = 0; it < kStoreIters; it++) {
-				uint32_t w[4];
-#pragma unroll
-				for (int t = 0; t < 4; t++) w[t] = sp[t][it * kStepBlocks * kLimbStride];
-				if (!(BS_DBG(P) & 2)) st_stream(g0 + (uint32_t)(4 * (tid + it * NT)), make_uint4(w[0], w[1], w[2], w[3]));
-			}
-		} else {
+			for (int t = 0; t < 4; t++) w[t] = sp[t][it * kStepBlocks * kLimbStride];
+			if (!(BS_DBG(P) & 2)) st_stream(g0 + (uint32_t)(4 * (tid + it * NT)), make_uint4(w[0], w[1], w[2], w[3]));
+		}
+	} else {
 #pragma unroll 4
-			for (int r = 0; r < kTileBlocks * 8 / 64; r++) {
-				const int u = lane + r * 64;
-				const int q = u >> 3, j = u & 7;
-				const uint4 g = *(const uint4*)(plane + q * kLimbStride + 4 * j);
-				if (!(BS_DBG(P) & 2)) st_stream(dst + (outer_off | tile_off(q)) * L + 32 * l + 4 * j, g);
-			}
+		for (int r = 0; r < kTileBlocks * 8 / 64; r++) {
+			const int u = lane + r * 64;
+			const int q = u >> 3, j = u & 7;
+			const uint4 g = *(const uint4*)(plane + q * kLimbStride + 4 * j);
+			if (!(BS_DBG(P) & 2)) st_stream(dst + (outer_off | tile_off(q)) * L + 32 * l + 4 * j, g);
 		}
-		if (TR) {
-			tr[3] += ts() - t1;
-			tr[4] += 1;
-		}
-		if (!PF || !has_next) break;
-		tile = next;
-		outer = n_outer_v;
-		outer_off = n_ooff;
-		coset = n_coset;
-		dst = n_dst;
-		src = n_src;
+	}
+	if (TR) {
+		tr[3] += ts() - t1;
+		tr[4] += 1;
 	}
 	if (TR && lane == 0) {
 		unsigned long long* o = P.trace + ((size_t)blockIdx.x * (NT / 64) + (tid >> 6)) * 8;
@@ -501,48 +461,10 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P, size_t tile0) {
 	}
 }
 
-template <int L, int ROLE, int FMAX, bool PF>
+template <int L, int ROLE, int FMAX>
 __global__ __launch_bounds__(64 * L, 2) void antt_bs_pass(BsParams P) {
-	bs_pass_body<L, ROLE, FMAX, PF>(P, blockIdx.x);
+	bs_pass_body<L, ROLE, FMAX>(P);
 }
-
-#ifdef BN_DEV
-// ------------------------------------------------------------------------------------
-// Experiment (development build only, BN_PERSIST3=1, EXPERIMENTS.md section 5.1): a
-// three-pass plan whose passes have at most two tiles per CU (one 2^20 transform: 256 tiles each)
-// as ONE launch of the variant-1 pass bodies with a grid-wide barrier between the passes instead of
-// kernel boundaries. Every work-group is resident, so the barrier cannot deadlock. Measured 0.157
-// ms against 0.0825 ms for the three launches (EXPERIMENTS.md section 5.1, round 5): not used.
-// ------------------------------------------------------------------------------------
-__device__ __forceinline__ void grid_barrier(unsigned* bar, unsigned target) {
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		__threadfence();  // agent-scope release of this work-group's stores (other XCDs read them)
-		atomicAdd(bar, 1u);
-		while (__hip_atomic_load(bar, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) __builtin_amdgcn_s_sleep(1);
-	}
-	__syncthreads();
-}
-
-struct BsParams3 {
-	BsParams p[3];
-};
-template <int F0, int F1>
-__global__ __launch_bounds__(256, 2) void antt_bs_persist3(BsParams3 Q, unsigned* bar, unsigned base) {
-	bs_pass_body<4, ROLE_FIRST, F0, false>(Q.p[0], blockIdx.x);
-	grid_barrier(bar, base + gridDim.x);
-	bs_pass_body<4, ROLE_MID, F1, false>(Q.p[1], blockIdx.x);
-	grid_barrier(bar, base + 2 * gridDim.x);
-	bs_pass_body<4, ROLE_LAST, 32, false>(Q.p[2], blockIdx.x);
-}
-
-static const void* persist3_kernel(int f0, int f1) {
-	if (f0 <= 8) return f1 <= 8 ? (const void*)antt_bs_persist3<8, 8> : (const void*)antt_bs_persist3<8, 32>;
-	return f1 <= 8 ? (const void*)antt_bs_persist3<32, 8> : (const void*)antt_bs_persist3<32, 32>;
-}
-#endif
-
-
 
 // ------------------------------------------------------------------------------------
 // Lane-split passes (small launches). A pass of T tiles runs 4T waves above; below two tiles per CU
@@ -563,17 +485,17 @@ static size_t split_lds_bytes() { return ((size_t)8 * kPlane + (size_t)kMaxStage
 
 template <int ROLE>
 __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
+	static_assert(ROLE == ROLE_FIRST || ROLE == ROLE_MID, "upper passes only: bitsliced out, no in-word stages");
 	extern __shared__ uint32_t lds[];
 	constexpr int L = 4;
-	constexpr bool IN_COMPACT = ROLE == ROLE_FIRST || ROLE == ROLE_SINGLE;
-	constexpr bool LAST = ROLE == ROLE_LAST || ROLE == ROLE_SINGLE;
+	constexpr bool IN_COMPACT = ROLE == ROLE_FIRST;
 	const BsPass& ps = P.p;
 	const int tid = threadIdx.x;
 	const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-	// BN_TRACE (development build): per-wave cycles of load, block stages, in-word stages +
-	// transposes, store
+	// BN_TRACE (development build): per-wave cycles of load, block stages, store (tr[0], tr[1],
+	// tr[3]: antt_bs_pass's slots) and of the multiplies inside the block stages (tr[6])
 	const bool TR = BS_TRACE(P);
-	unsigned long long tr[6] = {0, 0, 0, 0, 0, 0}, tlast = TR ? __builtin_amdgcn_s_memtime() : 0;
+	unsigned long long tr[8] = {0, 0, 0, 0, 1, 0, 0, 0}, tlast = TR ? __builtin_amdgcn_s_memtime() : 0;
 	auto mark = [&](int k) {
 		if (!TR) return;
 		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -637,18 +559,15 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 		}
 	}
 	__syncthreads();
-	auto transpose_blocks = [&](uint32_t* base) {
+	if (IN_COMPACT) {
 		// 512 per-(block, limb) 32x32 transposes, one per thread
-		uint32_t* x = base + (tid >> 7) * kPlane + (tid & 127) * kLimbStride;
+		uint32_t* x = lds + (tid >> 7) * kPlane + (tid & 127) * kLimbStride;
 		uint32_t r[32];
 #pragma unroll
 		for (int i = 0; i < 32; i += 4) *(uint4*)(r + i) = *(const uint4*)(x + i);
 		transpose32(r);
 #pragma unroll
 		for (int i = 0; i < 32; i += 4) *(uint4*)(x + i) = *(const uint4*)(r + i);
-	};
-	if (IN_COMPACT) {
-		transpose_blocks(lds);
 		__syncthreads();
 	}
 	// the stages, instantiated per product half H (its words o = 16 H index register arrays, so they
@@ -699,8 +618,7 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 	};
 
 	// ---- tile-bit stages: lane = block pair of limb l, as antt_bs_pass
-	const int jlow = max(LAST ? 5 : 0, ps.stop_j);
-	for (int j = ps.k - 1; j >= jlow; j--) {
+	for (int j = ps.k - 1; j >= 0; j--) {
 		const int m = ps.stage_m[j];
 		const int qu = ((lane >> m) << (m + 1)) | (lane & ((1 << m) - 1));
 		const int qv = qu | (1 << m);
@@ -717,9 +635,9 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 			W0[i] = (uint32_t)__builtin_amdgcn_sbfe(wt, i, 1);
 			W1[i] = (uint32_t)__builtin_amdgcn_sbfe(wt, 16 + i, 1);
 		}
-		if (TR) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tr[4] -= __builtin_amdgcn_s_memtime(); }
+		if (TR) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tr[6] -= __builtin_amdgcn_s_memtime(); }
 		half_product(ps.field[j], V, W0, W1, pr);
-		if (TR) { uint32_t acc = 0; for (int q = 0; q < 16; q++) acc ^= pr[q]; asm volatile("" ::"v"(acc)); tr[4] += __builtin_amdgcn_s_memtime(); }
+		if (TR) { uint32_t acc = 0; for (int q = 0; q < 16; q++) acc ^= pr[q]; asm volatile("" ::"v"(acc)); tr[6] += __builtin_amdgcn_s_memtime(); }
 #pragma unroll
 		for (int i = 0; i < 16; i += 4) {
 			uint4 uu = *(const uint4*)(su + o + i);
@@ -730,87 +648,21 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 		__syncthreads();
 		cur ^= 1;
 	}
-	mark(1);
-
-	if (LAST) {
-		// ---- stages 4..0 inside the words (antt_bs_pass's packing: lane owns blocks qa = lane and
-		// qb = lane + 64 of limb l; A's v-lanes move onto the u positions, B's stay)
-		const int qa = lane, qb = qa | (kTileBlocks / 2);
-		for (int s = 4; s >= ps.stop_j; s--) {
-			const uint32_t d = vgpr(1u << s);
-			const uint32_t um = vgpr(~lane_mask(s));
-			const uint32_t* sa = lds + cur * 4 * kPlane + l * kPlane + qa * kLimbStride;
-			const uint32_t* sb = lds + cur * 4 * kPlane + l * kPlane + qb * kLimbStride;
-			uint32_t* da = lds + (cur ^ 1) * 4 * kPlane + l * kPlane + qa * kLimbStride;
-			uint32_t* db = lds + (cur ^ 1) * 4 * kPlane + l * kPlane + qb * kLimbStride;
-			const uint32_t cb = cu_w[s] ^ tile_tw(s, qb);
-			uint32_t T[32], W0[16], W1[16], pr[16];
-#pragma unroll
-			for (int i = 0; i < 32; i += 4) {
-				const uint4 a = *(const uint4*)(sa + i), b = *(const uint4*)(sb + i);
-				T[i] = __builtin_amdgcn_bitop3_b32(a.x >> d, b.x, um, 0xe4);
-				T[i + 1] = __builtin_amdgcn_bitop3_b32(a.y >> d, b.y, um, 0xe4);
-				T[i + 2] = __builtin_amdgcn_bitop3_b32(a.z >> d, b.z, um, 0xe4);
-				T[i + 3] = __builtin_amdgcn_bitop3_b32(a.w >> d, b.w, um, 0xe4);
-			}
-			// twiddle words: the bit-lane pattern plus the block part (antt_bs_pass)
-#pragma unroll
-			for (int i = 0; i < 16; i++) {
-				W0[i] = ps.pat[s][i] ^ (uint32_t)__builtin_amdgcn_sbfe(cb, i, 1);
-				W1[i] = ps.pat[s][16 + i] ^ (uint32_t)__builtin_amdgcn_sbfe(cb, 16 + i, 1);
-			}
-			half_product(ps.field[s], T, W0, W1, pr);
-#pragma unroll
-			for (int i = 0; i < 16; i += 4) {
-				uint32_t A[4], Bv[4];
-				*(uint4*)A = *(const uint4*)(sa + o + i);
-				*(uint4*)Bv = *(const uint4*)(sb + o + i);
-#pragma unroll
-				for (int c = 0; c < 4; c++) {
-					const uint32_t a = __builtin_amdgcn_bitop3_b32(pr[i + c], um, A[c], 0x6a);
-					const uint32_t b = __builtin_amdgcn_bitop3_b32(pr[i + c] >> d, um, Bv[c], 0x6a);
-					A[c] = __builtin_amdgcn_bitop3_b32(a << d, um, a, 0x9a);
-					Bv[c] = __builtin_amdgcn_bitop3_b32(b << d, um, b, 0x9a);
-				}
-				*(uint4*)(da + o + i) = *(const uint4*)A;
-				*(uint4*)(db + o + i) = *(const uint4*)Bv;
-			}
-			__syncthreads();
-			cur ^= 1;
-		}
-	}
 	return cur;
 	};
 	mark(0);
 	const int cur = half == 0 ? stages(std::integral_constant<int, 0>()) : stages(std::integral_constant<int, 1>());
-	mark(2);
-	if (LAST) {
-		// back to compact words
-		uint32_t* const fin = lds + cur * 4 * kPlane;
-		transpose_blocks(fin);
-		__syncthreads();
-		for (int u = tid; u < kTileBlocks * 8 * L; u += kSplitNT) {
-			const int q = u / (8 * L), j = u % (8 * L);
-			uint32_t wd[4];
-#pragma unroll
-			for (int c = 0; c < 4; c++) {
-				const int word = 4 * j + c;
-				wd[c] = fin[(word % L) * kPlane + q * kLimbStride + word / L];
-			}
-			if (!(BS_DBG(P) & 2)) st_stream(dst + (ooff | tile_off(q)) * L + 4 * j, make_uint4(wd[0], wd[1], wd[2], wd[3]));
-		}
-	} else {
-		const uint32_t* const fin = lds + cur * 4 * kPlane;
-		for (int u = tid; u < kTileBlocks * 8 * L; u += kSplitNT) {
-			const int pl = u >> 10, r = u & 1023, q = r >> 3, j = r & 7;
-			const uint4 g = *(const uint4*)(fin + pl * kPlane + q * kLimbStride + 4 * j);
-			if (!(BS_DBG(P) & 2)) st_stream(dst + (ooff | tile_off(q)) * L + 32 * pl + 4 * j, g);
-		}
+	mark(1);
+	const uint32_t* const fin = lds + cur * 4 * kPlane;
+	for (int u = tid; u < kTileBlocks * 8 * L; u += kSplitNT) {
+		const int pl = u >> 10, r = u & 1023, q = r >> 3, j = r & 7;
+		const uint4 g = *(const uint4*)(fin + pl * kPlane + q * kLimbStride + 4 * j);
+		if (!(BS_DBG(P) & 2)) st_stream(dst + (ooff | tile_off(q)) * L + 32 * pl + 4 * j, g);
 	}
 	mark(3);
 	if (TR && lane == 0) {
 		unsigned long long* o = P.trace + ((size_t)blockIdx.x * (kSplitNT / 64) + w) * 8;
-		o[0] = tr[0], o[1] = tr[1], o[2] = tr[2], o[3] = tr[3], o[4] = 1, o[5] = tr[4], o[6] = 0, o[7] = 0;
+		for (int i = 0; i < 8; i++) o[i] = tr[i];
 	}
 }
 
@@ -879,13 +731,9 @@ static std::vector<BsPass> plan_passes(const bn_antt_plan* plan) {
 		}
 		return p;
 	};
-	// stages of the bottom pass: all 12 of a tile by default. BN_BOTTOM_K=11 (development build,
-	// VERDICT r5 item 5) moves its top block stage into the last upper pass (2^24: 7 + 6 + 11)
-	int bottom_k = kMinLogH;
-#ifdef BN_DEV
-	if (const char* e = getenv("BN_BOTTOM_K")) bottom_k = std::max(kMinLogH - 1, std::min(kMinLogH, atoi(e)));
-#endif
-	if (log_h - bottom_k < 1) bottom_k = kMinLogH;
+	// the bottom pass runs all 12 stages of a tile (7 + 6 + 11 at 2^24 measured slower: DESIGN.md
+	// section 5.6)
+	constexpr int bottom_k = kMinLogH;
 	const int rest = log_h - bottom_k;
 	const int n_up = (rest + kBlkBits - 1) / kBlkBits;
 	auto gf8_stage = [&](int s) {
@@ -898,7 +746,6 @@ static std::vector<BsPass> plan_passes(const bn_antt_plan* plan) {
 	for (int i = 0; i < n_up; i++) {
 		const int remaining_up = n_up - i;
 		int k = (hi - bottom_k + remaining_up - 1) / remaining_up;
-#ifndef BN_UP_EVEN
 		// the first pass takes every top stage whose twiddles lie in GF(2^8) (up to a tile's 7 bits,
 		// as long as the later passes still fit): its register-tile kernel runs near the HBM rate with
 		// VALU to spare, and each stage it takes leaves the GF(2^32) pass one stage less
@@ -907,8 +754,7 @@ static std::vector<BsPass> plan_passes(const bn_antt_plan* plan) {
 			while (g < kBlkBits && hi - g - 1 >= bottom_k && gf8_stage(hi - g - 1)) g++;
 			const int min_first = (hi - bottom_k) - (remaining_up - 1) * kBlkBits;  // the rest must still fit
 			if (g > k && g >= min_first) k = g;
-		BN_DEV_FIRST_K(k, min_first); }  // development build: BN_FIRST_K=k overrides the first pass's stage count
-#endif
+		}
 		passes.push_back(make(hi - k, k, false));
 		hi -= k;
 	}
@@ -920,37 +766,24 @@ static std::vector<BsPass> plan_passes(const bn_antt_plan* plan) {
 	return passes;
 }
 
-// kernel instance per (limbs, role, largest stage field); passes whose stages all use GF(2^8)
-// twiddles have registers to spare for prefetching the next tile
-// next-tile prefetch (BN_PF, persistent grid) is a development-build experiment: the product
-// build does not instantiate those kernels
-#ifdef BN_DEV
-#define BS_KERNEL(R) (pf ? (const void*)antt_bs_pass<L, R, FMAX, true> : (const void*)antt_bs_pass<L, R, FMAX, false>)
-#else
-#define BS_KERNEL(R) ((void)pf, (const void*)antt_bs_pass<L, R, FMAX, false>)
-#endif
+// kernel instance per (limbs, role, largest stage field)
 template <int L, int FMAX>
-static const void* kernel_for_f(int role, bool pf) {
+static const void* kernel_for_f(int role) {
 	switch (role) {
-		case ROLE_FIRST: return BS_KERNEL(ROLE_FIRST);
-		case ROLE_MID: return BS_KERNEL(ROLE_MID);
-		case ROLE_LAST: return BS_KERNEL(ROLE_LAST);
-		default: return BS_KERNEL(ROLE_SINGLE);
+		case ROLE_FIRST: return (const void*)antt_bs_pass<L, ROLE_FIRST, FMAX>;
+		case ROLE_MID: return (const void*)antt_bs_pass<L, ROLE_MID, FMAX>;
+		case ROLE_LAST: return (const void*)antt_bs_pass<L, ROLE_LAST, FMAX>;
+		default: return (const void*)antt_bs_pass<L, ROLE_SINGLE, FMAX>;
 	}
 }
-#undef BS_KERNEL
-static const void* kernel_for(int L, int role, int fmax, bool pf) {
-	if (L == 4) return fmax <= 8 ? kernel_for_f<4, 8>(role, pf) : kernel_for_f<4, 32>(role, pf);
-	return fmax <= 8 ? kernel_for_f<1, 8>(role, pf) : kernel_for_f<1, 32>(role, pf);
+static const void* kernel_for(int L, int role, int fmax) {
+	if (L == 4) return fmax <= 8 ? kernel_for_f<4, 8>(role) : kernel_for_f<4, 32>(role);
+	return fmax <= 8 ? kernel_for_f<1, 8>(role) : kernel_for_f<1, 32>(role);
 }
 
+// lane-split kernels: upper passes only (use_split)
 static const void* split_kernel_for(int role) {
-	switch (role) {
-		case ROLE_FIRST: return (const void*)antt_bs3_pass<ROLE_FIRST>;
-		case ROLE_MID: return (const void*)antt_bs3_pass<ROLE_MID>;
-		case ROLE_LAST: return (const void*)antt_bs3_pass<ROLE_LAST>;
-		default: return (const void*)antt_bs3_pass<ROLE_SINGLE>;
-	}
+	return role == ROLE_FIRST ? (const void*)antt_bs3_pass<ROLE_FIRST> : (const void*)antt_bs3_pass<ROLE_MID>;
 }
 
 // plan_passes gives the bottom pass the tile bits bb[m] = 5 + m; its kernels rely on it
@@ -977,16 +810,9 @@ int bs_prepare(bn_antt_plan* plan) {
 	for (int L : {1, 4})
 		for (int role = 0; role < 4; role++)
 			for (int f : {8, 32})
-				for (int pf = 0; pf < 2; pf++)
-					BN_HIP(hipFuncSetAttribute(kernel_for(L, role, f, pf != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
-					                           (int)lds_bytes(L)));
-	for (int role = 0; role < 4; role++)
+				BN_HIP(hipFuncSetAttribute(kernel_for(L, role, f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(L)));
+	for (int role : {ROLE_FIRST, ROLE_MID})
 		BN_HIP(hipFuncSetAttribute(split_kernel_for(role), hipFuncAttributeMaxDynamicSharedMemorySize, (int)split_lds_bytes()));
-#ifdef BN_DEV
-	for (int f0 : {8, 32})
-		for (int f1 : {8, 32})
-			BN_HIP(hipFuncSetAttribute(persist3_kernel(f0, f1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(4)));
-#endif
 	// the pass tables are built here, once per plan, so that a bottom pass whose tile is not the
 	// contiguous run its kernels address fails the plan and never reaches a launch
 	size_t n_passes = 0;
@@ -1052,26 +878,24 @@ extern "C" int bn_antt_inword_tables(int log_h, int log_rate, uint32_t* out, siz
 namespace bn {
 
 struct BsDevKnobs {
-	int pf_mode = 0, dbg = 0, stop_stage = -1, split = -1, mid_pf = -1, rr_last = -1;
-	bool persist = true, trace = false;
-	size_t max_passes = ~(size_t)0;
+	int dbg = 0, split = -1, rr_last = -1;
+	bool trace = false;
 };
 
+// The environment switches of the development build (make BN_DEV=1), all of them. The product
+// build reads none. They measure or select among kernels the product itself launches:
+//   BN_DEBUG_FLAGS=bits  skip work for timing (wrong results): 1 no tile loads, 2 no tile stores,
+//                        4 no multiplies (antt_bs_pass; antt_rr_pass takes bits 1 and 2, antt_bs3_pass bit 2)
+//   BN_TRACE=1           per-wave phase times in cycles on stderr (antt_bs_pass, antt_bs3_pass)
+//   BN_SPLIT=0/1         upper GF(2^16/32) passes never / always on the lane-split kernel
+//   BN_RR_LAST=0         small bottom passes stay on LDS tiles
+//   BN_ANTT_VARIANT=v    kernel variant of new plans (antt.hip)
 static BsDevKnobs dev_knobs() {
 	BsDevKnobs k;
 #ifdef BN_DEV
-	// development build only (make BN_DEV=1): BN_DEBUG_MAX_PASSES=n runs only the first n passes,
-	// BN_DEBUG_STOP_STAGE=s runs only stages >= s, BN_DEBUG_FLAGS skips work (see BsParams::dbg),
-	// BN_PF=1/2 enables next-tile prefetch for GF(2^8)-only / all passes, BN_PERSIST=0 launches
-	// one workgroup per tile, BN_TRACE=1 prints per-wave phase times (cycles)
-	if (const char* e = getenv("BN_DEBUG_MAX_PASSES")) k.max_passes = (size_t)atoi(e);
-	if (const char* e = getenv("BN_PF")) k.pf_mode = atoi(e);
-	if (const char* e = getenv("BN_PERSIST")) k.persist = atoi(e) != 0;
-	if (const char* e = getenv("BN_DEBUG_FLAGS")) k.dbg = atoi(e);
-	if (const char* e = getenv("BN_DEBUG_STOP_STAGE")) k.stop_stage = atoi(e);
-	if (const char* e = getenv("BN_SPLIT")) k.split = atoi(e);  // 0: never lane-split, 1: always
-	if (const char* e = getenv("BN_MID_PF")) k.mid_pf = atoi(e);  // 1: middle passes on antt_rr_mid_pf
-	if (const char* e = getenv("BN_RR_LAST")) k.rr_last = atoi(e);  // 0: small bottom passes on LDS tiles
+	if (const char* e = getenv("BN_DEBUG_FLAGS")) k.dbg = atoi(e) & 7;
+	if (const char* e = getenv("BN_SPLIT")) k.split = atoi(e);
+	if (const char* e = getenv("BN_RR_LAST")) k.rr_last = atoi(e);
 	k.trace = getenv("BN_TRACE") != nullptr;
 #endif
 	return k;
@@ -1080,46 +904,65 @@ static BsDevKnobs dev_knobs() {
 // GF(2^16/32) LDS-tile upper passes of fewer tiles than two per CU (one 2^20 transform) run
 // lane-split (antt_bs3_pass: two waves per product, two waves per SIMD instead of one). 2^20 A/B
 // (EXPERIMENTS.md section 5.1, round 4): upper GF(2^32) pass 0.0139 vs 0.0158 ms, bottom pass 0.0514 vs 0.0496 ms,
-// so the bottom pass keeps one wave per limb (EXPERIMENTS.md section 5.1, round 4)
-// Development build only (BN_MID_PF=1): GF(2^16/32) middle passes on antt_rr_mid_pf, the
-// register-tile kernel that hides the next tile's loads. Measured slower than antt_bs_pass at 2^24
-// (pass 1 0.224-0.229 vs 0.189-0.193 ms), so the product never selects it.
-static bool use_mid_pf(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
-#ifdef BN_DEV
-	if (kn.mid_pf != 1) return false;
-	if (plan->variant != 5 || plan->limbs != 4 || pass.role != ROLE_MID || pass_fmax(pass) <= 8) return false;
-	RtPass rt;
-	if (make_rt(pass, false, &rt) != BN_OK) return false;
-	return ntiles >= (size_t)8 * (size_t)plan->num_cus;
-#else
-	(void)plan, (void)pass, (void)ntiles, (void)kn;
-	return false;
-#endif
-}
-
+// so the bottom pass keeps one wave per limb and has no lane-split kernel
 static bool use_split(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
 	if (plan->limbs != 4 || pass_fmax(pass) <= 8) return false;
-	if (kn.split >= 0) return kn.split != 0;
 	if (pass.role == ROLE_LAST || pass.role == ROLE_SINGLE) return false;
+	if (kn.split >= 0) return kn.split != 0;
 	return ntiles < (size_t)2 * (size_t)plan->num_cus;
 }
 
 // Bottom pass of a small launch (fewer tiles than two per CU: one wave per SIMD either way) on
-// register tiles, compiled without the three-waves bound (antt_rr.hip small_last): C3 (one 2^20
+// register tiles, compiled without the three-waves bound (antt_rr.hip rr_pass_kernel): C3 (one 2^20
 // transform) 0.0800-0.0802 vs 0.0822-0.0824 ms on LDS tiles (round 5, EXPERIMENTS.md section 5.1).
-// BN_RR_LAST=0 (development build) keeps it on LDS tiles.
 static bool use_rr_last(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
 	if (kn.rr_last == 0 || plan->variant != 5 || plan->limbs != 4 || pass.role != ROLE_LAST) return false;
 	return ntiles < (size_t)2 * (size_t)plan->num_cus;
 }
 
-static int launch_one(bn_antt_plan* plan, const BsPass& pass, int i, const uint32_t* d_in, uint32_t* d_out,
-                      size_t batch, hipStream_t st, const BsDevKnobs& kn) {
+// What runs a pass of `ntiles` tiles (one workgroup per tile). The only place that decides it:
+// launch_one launches what this returns and bs_pass_kernel reports it.
+struct BsSel {
+	const void* kernel;  // nullptr: the plan's variant has no bitsliced passes
+	bool rr;             // a register-tile kernel: rr_launch_pass launches it (RrParams, its own geometry)
+	unsigned threads;    // otherwise: workgroup size and dynamic LDS of a BsParams kernel of this file
+	size_t lds;
+};
+static BsSel select_pass(bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
+	const int L = plan->limbs, fmax = pass_fmax(pass);
 	// variant 4: every pass on register tiles; variant 5 (mixed): register tiles for the passes whose
 	// twiddles all lie in GF(2^8) (their kernel fits four waves per SIMD), LDS tiles for the others
-	if (plan->variant == 4 || (plan->variant == 5 && pass_fmax(pass) <= 8)) return rr_launch_pass(plan, i, d_in, d_out, batch, st);
-	if (use_rr_last(plan, pass, (batch << plan->log_rate) << pass.n_outer, kn)) return rr_launch_pass(plan, i, d_in, d_out, batch, st);
-	const int L = plan->limbs;
+	if (plan->variant == 4 || (plan->variant == 5 && fmax <= 8) || use_rr_last(plan, pass, ntiles, kn))
+		return {rr_pass_kernel(plan, pass, ntiles), true, 0, 0};
+	if (plan->variant != 1 && plan->variant != 5) return {nullptr, false, 0, 0};
+	if (use_split(plan, pass, ntiles, kn)) return {split_kernel_for(pass.role), false, kSplitNT, split_lds_bytes()};
+	return {kernel_for(L, pass.role, fmax), false, 64u * (unsigned)L, lds_bytes(L)};
+}
+
+// BN_TRACE: the phase cycles the waves of one launch left in d_trace (8 words per wave, the slots of
+// tr[] in antt_bs_pass), as averages per wave-tile
+static int print_trace(int i, const BsSel& sel, int fmax, const unsigned long long* d_trace, size_t waves, hipStream_t st) {
+	std::vector<unsigned long long> h(waves * 8);
+	BN_HIP(hipStreamSynchronize(st));
+	BN_HIP(hipMemcpy(h.data(), d_trace, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost));
+	double acc[8] = {0};
+	for (size_t w = 0; w < waves; w++)
+		for (int k = 0; k < 8; k++) acc[k] += (double)h[w * 8 + k];
+	const double t = acc[4] > 0 ? acc[4] : 1;  // wave-tiles
+	fprintf(stderr,
+	        "trace pass %d (%s, fmax %d, %zu wave-tiles, cycles per wave-tile): load %.0f  block %.0f [pre %.0f mul %.0f post %.0f]  "
+	        "inword+tr %.0f  store %.0f\n",
+	        i, sel.threads == kSplitNT ? "split" : "tile", fmax, (size_t)acc[4], acc[0] / t, acc[1] / t, acc[5] / t, acc[6] / t,
+	        acc[7] / t, acc[2] / t, acc[3] / t);
+	return BN_OK;
+}
+
+static int launch_one(bn_antt_plan* plan, const BsPass& pass, int i, const uint32_t* d_in, uint32_t* d_out,
+                      size_t batch, hipStream_t st, const BsDevKnobs& kn) {
+	const size_t ntiles = (batch << plan->log_rate) << pass.n_outer;
+	const BsSel sel = select_pass(plan, pass, ntiles, kn);
+	if (sel.rr) return rr_launch_pass(plan, i, d_in, d_out, batch, st);
+	if (!sel.kernel) BN_FAIL(BN_ERR_UNSUPPORTED, "variant %d has no bitsliced passes", plan->variant);
 	BsParams prm;
 	prm.src = d_in;
 	prm.dst = d_out;
@@ -1127,69 +970,23 @@ static int launch_one(bn_antt_plan* plan, const BsPass& pass, int i, const uint3
 	prm.log_rate = plan->log_rate;
 	prm.dbg = kn.dbg;
 	prm.p = pass;
-	prm.p.stop_j = kn.stop_stage < 0 ? 0 : std::max(0, std::min(prm.p.k, kn.stop_stage - prm.p.lo));
-	const size_t ntiles = (batch << plan->log_rate) << pass.n_outer;
-#ifdef BN_DEV
-	if (use_mid_pf(plan, pass, ntiles, kn)) return rr_launch_mid_pf(plan, i, d_in, d_out, batch, st);
-#endif
-	if (use_split(plan, pass, ntiles, kn)) {
-		prm.ntiles = ntiles;
-		prm.trace = nullptr;
-		static unsigned long long* strbuf = nullptr;
-		if (kn.trace) {
-			if (!strbuf) BN_HIP(hipMalloc(&strbuf, (size_t)1 << 26));
-			BN_HIP(hipMemset(strbuf, 0, ntiles * 8 * 8 * 8));
-			prm.trace = strbuf;
-		}
-		int rc = timing_begin(plan, i, st);
-		if (rc != BN_OK) return rc;
-		void* args[] = {&prm};
-		BN_HIP(hipLaunchKernel(split_kernel_for(pass.role), dim3((unsigned)ntiles), dim3(kSplitNT), args, split_lds_bytes(), st));
-		rc = timing_end(plan, i, st);
-		if (rc != BN_OK || !prm.trace) return rc;
-		std::vector<unsigned long long> h(ntiles * 8 * 8);
-		BN_HIP(hipStreamSynchronize(st));
-		BN_HIP(hipMemcpy(h.data(), prm.trace, h.size() * 8, hipMemcpyDeviceToHost));
-		double acc[6] = {0};
-		for (size_t wv = 0; wv < ntiles * 8; wv++)
-			for (int k = 0; k < 6; k++) acc[k] += (double)h[wv * 8 + k];
-		const double t = acc[4] > 0 ? acc[4] : 1;
-		fprintf(stderr, "trace pass %d (split, %zu waves, cycles per wave): load %.0f  block %.0f [mul %.0f]  inword+tr %.0f  store %.0f\n", i,
-		        (size_t)acc[4], acc[0] / t, acc[1] / t, acc[5] / t, acc[2] / t, acc[3] / t);
-		return BN_OK;
-	}
-	// two 74-KB tiles per CU: a persistent grid of two workgroups per CU walks all tiles
-	const int fmax = pass_fmax(pass);
-	const bool pf = kn.persist && (kn.pf_mode == 2 || (kn.pf_mode == 1 && fmax <= 8));
-	const size_t grid = pf ? std::min(ntiles, (size_t)2 * (size_t)plan->num_cus) : ntiles;
-	prm.ntiles = ntiles;
 	prm.trace = nullptr;
-	static unsigned long long* trbuf = nullptr;
+	const size_t waves = ntiles * (sel.threads / 64);
 	if (kn.trace) {
-		if (!trbuf) BN_HIP(hipMalloc(&trbuf, (size_t)1 << 26));
-		BN_HIP(hipMemset(trbuf, 0, grid * L * 8 * 8));
+		constexpr size_t kTraceBytes = (size_t)1 << 26;
+		static unsigned long long* trbuf = nullptr;
+		if (waves * 8 * sizeof(*trbuf) > kTraceBytes) BN_FAIL(BN_ERR_UNSUPPORTED, "BN_TRACE: %zu waves do not fit the trace buffer", waves);
+		if (!trbuf) BN_HIP(hipMalloc(&trbuf, kTraceBytes));
+		BN_HIP(hipMemsetAsync(trbuf, 0, waves * 8 * sizeof(*trbuf), st));
 		prm.trace = trbuf;
 	}
 	int rc = timing_begin(plan, i, st);
 	if (rc != BN_OK) return rc;
 	void* args[] = {&prm};
-	BN_HIP(hipLaunchKernel(kernel_for(L, pass.role, fmax, pf), dim3((unsigned)grid), dim3(64 * L), args, lds_bytes(L), st));
+	BN_HIP(hipLaunchKernel(sel.kernel, dim3((unsigned)ntiles), dim3(sel.threads), args, sel.lds, st));
 	rc = timing_end(plan, i, st);
-	if (rc != BN_OK) return rc;
-	if (prm.trace) {
-		const size_t g = grid * (size_t)L;
-		std::vector<unsigned long long> h(g * 8);
-		BN_HIP(hipStreamSynchronize(st));
-		BN_HIP(hipMemcpy(h.data(), prm.trace, g * 8 * 8, hipMemcpyDeviceToHost));
-		double acc[8] = {0};
-		for (size_t w = 0; w < g; w++)
-			for (int k = 0; k < 8; k++) acc[k] += (double)h[w * 8 + k];
-		const double t = acc[4] > 0 ? acc[4] : 1;  // wave-tiles
-		fprintf(stderr,
-		        "trace pass %d (fmax %d pf %d, %zu wave-tiles, cycles per wave-tile): load %.0f  block %.0f [pre %.0f mul %.0f post %.0f]  inword+tr %.0f  store %.0f\n",
-		        i, fmax, (int)pf, (size_t)acc[4], acc[0] / t, acc[1] / t, acc[5] / t, acc[6] / t, acc[7] / t, acc[2] / t, acc[3] / t);
-	}
-	return BN_OK;
+	if (rc != BN_OK || !prm.trace) return rc;
+	return print_trace(i, sel, pass_fmax(pass), prm.trace, waves, st);
 }
 
 // the kernel pass i launches under the plan's variant (variants 1, 4, 5), nullptr otherwise
@@ -1197,69 +994,17 @@ const void* bs_pass_kernel(bn_antt_plan* plan, int i) {
 	size_t n_passes = 0;
 	const BsPass* passes = bs_passes(plan, &n_passes);
 	if (i < 0 || (size_t)i >= n_passes) return nullptr;
-	const BsPass& pass = passes[i];
-	const int fmax = pass_fmax(pass);
-	if (plan->variant == 4 || (plan->variant == 5 && fmax <= 8)) return rr_pass_kernel(plan, pass);
-	if (plan->variant != 1 && plan->variant != 5) return nullptr;
-	const BsDevKnobs kn = dev_knobs();
 	// the kernel for ONE transform (bench / profiles): a batched launch of the same pass may pick
-	// another (the lane-split and prefetching kernels depend on the tile count)
-	const size_t ntiles = ((size_t)1 << plan->log_rate) << pass.n_outer;
-#ifdef BN_DEV
-	if (use_mid_pf(plan, pass, ntiles, kn)) return rr_mid_pf_kernel(pass);
-#endif
-	if (use_rr_last(plan, pass, ntiles, kn)) return rr_pass_kernel(plan, pass);
-	if (use_split(plan, pass, ntiles, kn)) return split_kernel_for(pass.role);
-	const bool pf = kn.persist && (kn.pf_mode == 2 || (kn.pf_mode == 1 && fmax <= 8));
-	return kernel_for(plan->limbs, pass.role, fmax, pf);
+	// another (the lane-split and small-bottom kernels depend on the tile count)
+	const size_t ntiles = ((size_t)1 << plan->log_rate) << passes[i].n_outer;
+	return select_pass(plan, passes[i], ntiles, dev_knobs()).kernel;
 }
-
-
-#ifdef BN_DEV
-static int launch_persist3(bn_antt_plan* plan, const BsPass* passes, const uint32_t* d_in, uint32_t* d_out, size_t batch,
-                           hipStream_t st) {
-	static unsigned* d_bar = nullptr;
-	static unsigned gen = 0;
-	if (!d_bar) {
-		BN_HIP(hipMalloc(&d_bar, sizeof(unsigned)));
-		BN_HIP(hipMemset(d_bar, 0, sizeof(unsigned)));
-	}
-	BsParams3 q;
-	memset(&q, 0, sizeof q);
-	size_t ntiles = 0;
-	for (int i = 0; i < 3; i++) {
-		q.p[i].src = d_in;
-		q.p[i].dst = d_out;
-		q.p[i].log_h = plan->log_h;
-		q.p[i].log_rate = plan->log_rate;
-		q.p[i].p = passes[i];
-		ntiles = (batch << plan->log_rate) << passes[i].n_outer;
-		q.p[i].ntiles = ntiles;
-	}
-	unsigned base = gen * 2u * (unsigned)ntiles;
-	gen++;
-	int rc = timing_begin(plan, 0, st);
-	if (rc != BN_OK) return rc;
-	void* args[] = {&q, &d_bar, &base};
-	BN_HIP(hipLaunchKernel(persist3_kernel(pass_fmax(passes[0]), pass_fmax(passes[1])), dim3((unsigned)ntiles), dim3(256), args,
-	                       lds_bytes(4), st));
-	return timing_end(plan, 0, st);
-}
-#endif
 
 int launch_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st) {
 	size_t n_passes = 0;
 	const BsPass* passes = bs_passes(plan, &n_passes);
 	const BsDevKnobs kn = dev_knobs();
-#ifdef BN_DEV
-	if (getenv("BN_PERSIST3") && n_passes == 3 && plan->limbs == 4) {
-		bool ok = true;
-		for (int i = 0; i < 3; i++) ok = ok && ((batch << plan->log_rate) << passes[i].n_outer) <= (size_t)2 * (size_t)plan->num_cus;
-		if (ok) return launch_persist3(plan, passes, d_in, d_out, batch, st);
-	}
-#endif
-	const size_t npass = std::min(n_passes, kn.max_passes);
-	for (size_t i = 0; i < npass; i++) {
+	for (size_t i = 0; i < n_passes; i++) {
 		int rc = launch_one(plan, passes[i], (int)i, d_in, d_out, batch, st, kn);
 		if (rc != BN_OK) return rc;
 	}

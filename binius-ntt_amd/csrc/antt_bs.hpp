@@ -21,7 +21,7 @@ enum { ROLE_FIRST = 0, ROLE_MID = 1, ROLE_LAST = 2, ROLE_SINGLE = 3 };
 // One pass = k consecutive stages lo..lo+k-1 over every tile. Passed by value as a kernel
 // argument (~2.6 KB), so every table read is a scalar load from the kernarg segment.
 struct BsPass {
-	int lo, k, role, n_outer, stop_j;
+	int lo, k, role, n_outer;
 	int bb[kBlkBits];                        // index bit of tile block bit m
 	int ob[kMaxOuter];                       // fixed (outer) index bits, ascending
 	int stage_m[kMaxStages];                 // tile bit of stage lo + j (stages >= 5)
@@ -63,10 +63,8 @@ int make_rt(const BsPass& p, bool bottom, RtPass* out);
 // variant 4 (antt_rr.hip): register-tile kernels over the same passes
 int rr_prepare(bn_antt_plan* plan);
 int rr_launch_pass(bn_antt_plan* plan, int i, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st);
-const void* rr_pass_kernel(bn_antt_plan* plan, const BsPass& pass);
+// the register-tile kernel of a pass launched over `ntiles` tiles
+const void* rr_pass_kernel(bn_antt_plan* plan, const BsPass& pass, size_t ntiles);
 const void* bs_pass_kernel(bn_antt_plan* plan, int i);
-// middle passes with the next tile prefetched by LDS-DMA (antt_rr.hip antt_rr_mid_pf)
-int rr_launch_mid_pf(bn_antt_plan* plan, int i, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st);
-const void* rr_mid_pf_kernel(const BsPass& pass);
 
 }  // namespace bn

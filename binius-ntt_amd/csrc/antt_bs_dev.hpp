@@ -1,5 +1,6 @@
-// Device helpers shared by the bitsliced LDS-tile kernels of the additive NTT: the forward
-// passes (antt_bs.hip) and the inverse passes (antt_inv.hip).
+// Device helpers shared by the bitsliced kernels of the additive NTT: the forward LDS-tile passes
+// (antt_bs.hip), the inverse passes (antt_inv.hip) and the register-tile passes (antt_rr.hip, which
+// takes lane_mask and u32x4 from here).
 #pragma once
 
 #include <hip/hip_runtime.h>

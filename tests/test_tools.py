@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_trace_passes_phases(tmp_path):
     k, w = 5, 2
     ev, iso = max(5, min(k, 20)), 1 + max(10, min(k, 40))
-    names = ["void bn::antt_bs_pass<4, %d, 32, false>(bn::BsParams)" % r for r in range(3)]
+    names = ["void bn::antt_bs_pass<4, %d, 32>(bn::BsParams)" % r for r in range(3)]
     rows, t = [], 0
 
     def launch(r, dur):
