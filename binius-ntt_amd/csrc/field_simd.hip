@@ -13,6 +13,8 @@
 // primitive for callers and tests, not part of the NTT / sumcheck kernels.
 #include <hip/hip_runtime.h>
 
+#include <utility>
+
 #include "bitsliced_gen.hpp"
 #include "common.hpp"
 #include "tower.hpp"
@@ -81,6 +83,73 @@ __global__ __launch_bounds__(256) void k_unrolled(const uint32_t* a, const uint3
 	}
 }
 
+// Test hook behind bn_circuit_device: the generated circuits in the order of bitsliced_gen.hpp.
+// Words per block of a and out, words per block of a bitsliced b (0: b is compact), and whether
+// out is accumulated into.
+constexpr int kCircuits = 14;
+constexpr int kCircuitAWords[kCircuits] = {4, 8, 32, 32, 16, 32, 32, 32, 32, 32, 64, 128, 32, 64};
+constexpr int kCircuitBWords[kCircuits] = {4, 8, 0, 8, 16, 0, 16, 32, 0, 32, 64, 128, 0, 0};
+constexpr bool kCircuitAcc[kCircuits] = {false, false, true, true, false, true, true, false, true, true, false, false, false, true};
+
+// One block per lane of a flat launch: operands into register arrays, the circuit once, stores
+// for the blocks below nblk only. Waves wholly past the end leave before the wave-uniform
+// twiddle is read (one entry per 64 blocks: lane k of a 256-lane work-group is in wave k / 64).
+template <int ID>
+__global__ __launch_bounds__(256) void k_circuit(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                 uint32_t* __restrict__ o, size_t nblk) {
+	constexpr int NA = kCircuitAWords[ID], NB = kCircuitBWords[ID];
+	const size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+	if ((k & ~(size_t)63) >= nblk) return;
+	const bool live = k < nblk;
+	uint32_t x[NA], z[NA], y[NB ? NB : 1];
+#pragma unroll
+	for (int i = 0; i < NA; i++) {
+		x[i] = live ? a[NA * k + i] : 0u;
+		z[i] = live && kCircuitAcc[ID] ? o[NA * k + i] : 0u;
+	}
+#pragma unroll
+	for (int i = 0; i < NB; i++) y[i] = live ? b[NB * k + i] : 0u;
+	if constexpr (ID == 0)
+		bsm2_mul(x, y, z);
+	else if constexpr (ID == 1)
+		bsm3_mul(x, y, z);
+	else if constexpr (ID == 2)
+		bsm3x4_fma_tw(x, live ? b[k] : 0u, z);
+	else if constexpr (ID == 3)
+		bsm3x4_mul_acc(x, y, z);
+	else if constexpr (ID == 4)
+		bsm4_mul(x, y, z);
+	else if constexpr (ID == 5)
+		bsm4x2_fma_tw(x, live ? b[k] : 0u, z);
+	else if constexpr (ID == 6)
+		bsm4x2_mul_acc(x, y, z);
+	else if constexpr (ID == 7)
+		bsm5_mul(x, y, z);
+	else if constexpr (ID == 8)
+		bsm5_fma_tw(x, live ? b[k] : 0u, z);
+	else if constexpr (ID == 9)
+		bsm5_mul_acc(x, y, z);
+	else if constexpr (ID == 10)
+		bsm6_mul(x, y, z);
+	else if constexpr (ID == 11)
+		bsm7_mul(x, y, z);
+	else if constexpr (ID == 12)
+		bsm5_mul_w(x, (uint32_t)__builtin_amdgcn_readfirstlane((int)b[k >> 6]), z);
+	else
+		bsm6_fma_w2(x, (uint32_t)__builtin_amdgcn_readfirstlane((int)b[2 * (k >> 6)]),
+		            (uint32_t)__builtin_amdgcn_readfirstlane((int)b[2 * (k >> 6) + 1]), z);
+	if (live) {
+#pragma unroll
+		for (int i = 0; i < NA; i++) o[NA * k + i] = z[i];
+	}
+}
+
+template <int... IDS>
+const void* circuit_kernel(int id, std::integer_sequence<int, IDS...>) {
+	const void* fns[] = {(const void*)k_circuit<IDS>...};
+	return fns[id];
+}
+
 __global__ __launch_bounds__(256) void k_packed(int op, int h, const uint32_t* a, const uint32_t* b, uint32_t* c, uint32_t* d,
                                                 size_t n) {
 	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -136,6 +205,17 @@ extern "C" int bn_multiply_unrolled_device(int height, const void* a, const void
 	                      (const void*)k_unrolled<5>, (const void*)k_unrolled<6>};
 	void* args[] = {&a, &b, &dst, &nblocks};
 	BN_HIP(hipLaunchKernel(fns[height - 2], dim3(grid_for(nblocks)), dim3(256), args, 0, (hipStream_t)stream));
+	return BN_OK;
+}
+
+extern "C" int bn_circuit_device(int circuit, const void* d_a, const void* d_b, void* d_out, size_t n_blocks, void* stream) {
+	BN_CHECK_ARG(circuit >= 0 && circuit < kCircuits, "circuit must be in [0, %d] (got %d)", kCircuits - 1, circuit);
+	BN_CHECK_ARG(d_a && d_b && d_out, "NULL device pointer");
+	BN_CHECK_ARG(n_blocks <= ((size_t)1 << 30), "n_blocks must be at most 2^30");
+	if (!n_blocks) return BN_OK;
+	void* args[] = {&d_a, &d_b, &d_out, &n_blocks};
+	BN_HIP(hipLaunchKernel(circuit_kernel(circuit, std::make_integer_sequence<int, kCircuits>{}),
+	                       dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), args, 0, (hipStream_t)stream));
 	return BN_OK;
 }
 

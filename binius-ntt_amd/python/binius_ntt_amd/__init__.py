@@ -78,6 +78,7 @@ def lib():
         "bn_bitslice_device": (i32, [vp, sz, i32, vp]),
         "bn_multiply_unrolled": (i32, [i32, u32p, u32p, u32p]),
         "bn_multiply_unrolled_device": (i32, [i32, vp, vp, vp, sz, vp]),
+        "bn_circuit_device": (i32, [i32, vp, vp, vp, sz, vp]),
         "bn_mul_binary_tower_32b_simd": (i32, [i32, ctypes.c_uint32, ctypes.c_uint32, u32p]),
         "bn_interleave_32b": (i32, [i32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p]),
         "bn_xor_adjacent_32b": (i32, [i32, ctypes.c_uint32, u32p]),
@@ -498,6 +499,25 @@ def multiply_unrolled_device(height, a, b, out, stream=None):
         _check_device_tensor(t, a.numel(), nm)
     _check(lib().bn_multiply_unrolled_device(height, _ptr(a), _ptr(b), _ptr(out), a.numel() // w,
                                              _stream(stream, _dev_index(a))))
+
+
+# bn_circuit_device's circuits, in the order of csrc/bitsliced_gen.hpp: (name, words of a and out
+# per block, words of b, blocks that share those words of b: 64 for a wave-uniform twiddle)
+CIRCUITS = (("bsm2_mul", 4, 4, 1), ("bsm3_mul", 8, 8, 1), ("bsm3x4_fma_tw", 32, 1, 1), ("bsm3x4_mul_acc", 32, 8, 1),
+            ("bsm4_mul", 16, 16, 1), ("bsm4x2_fma_tw", 32, 1, 1), ("bsm4x2_mul_acc", 32, 16, 1), ("bsm5_mul", 32, 32, 1),
+            ("bsm5_fma_tw", 32, 1, 1), ("bsm5_mul_acc", 32, 32, 1), ("bsm6_mul", 64, 64, 1), ("bsm7_mul", 128, 128, 1),
+            ("bsm5_mul_w", 32, 1, 64), ("bsm6_fma_w2", 64, 2, 64))
+
+
+def circuit_device(circuit, a, b, out, n_blocks, stream=None):
+    """Test hook: generated circuit `circuit` (index into CIRCUITS) on n_blocks 32-product blocks,
+    one block per lane (bn_circuit_device). out is read first by the accumulate forms."""
+    if 0 <= circuit < len(CIRCUITS):
+        _, wa, wb, share = CIRCUITS[circuit]
+        words_b = wb * ((n_blocks + share - 1) // share)
+        for t, words, nm in ((a, wa * n_blocks, "a"), (b, words_b, "b"), (out, wa * n_blocks, "out")):
+            _check_device_tensor(t, words, nm)
+    _check(lib().bn_circuit_device(circuit, _ptr(a), _ptr(b), _ptr(out), n_blocks, _stream(stream, _dev_index(a))))
 
 
 def mul_binary_tower_32b_simd(height, a, b):

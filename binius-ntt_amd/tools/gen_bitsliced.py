@@ -13,8 +13,11 @@ gate). Differences that matter on CDNA4:
 * every multiplier is alias-safe (all inputs are read before any output is written).
 
 Word i of a bitsliced operand holds bit i (tower basis) of 32 independent field elements.
-Output: binius-ntt_amd/csrc/bitsliced_gen.hpp
+Output: binius-ntt_amd/csrc/bitsliced_gen.hpp, or the file given with -o / --output (the suite
+regenerates into a temporary file and compares it with the committed header). The gate count of
+every circuit is printed to stderr, in the header's order.
 """
+import argparse
 import os
 import sys
 
@@ -769,7 +772,10 @@ def fn(sig, lines):
     return "__host__ __device__ __forceinline__ " + sig + " {\n\t" + "\n\t".join(lines) + "\n}\n"
 
 
-def main():
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("-o", "--output", default=OUT, help="file to write (default: %(default)s)")
+    out_path = ap.parse_args(argv).output
     parts = ["// GENERATED by binius-ntt_amd/tools/gen_bitsliced.py -- do not edit.",
              "// Bitsliced binary-tower multipliers (Karatsuba tower, gfx950 v_bitop3 fusion).",
              "#pragma once", "#include <hip/hip_runtime.h>", "#include <stdint.h>", "",
@@ -830,7 +836,7 @@ def main():
     parts.append(fn("void bsm6_fma_w2(const uint32_t* __restrict__ a, uint32_t w0, uint32_t w1, uint32_t* __restrict__ out)", wl))
     stats.append((6, "fma_w2", count_ops(wl)))
     parts.append("}  // namespace bn")
-    with open(OUT, "w") as f:
+    with open(out_path, "w") as f:
         f.write("\n".join(parts) + "\n")
     for s in stats:
         print(s, file=sys.stderr)

@@ -172,6 +172,16 @@ int bn_bitslice_device(void* d_buf, size_t n_blocks, int untranspose, void* stre
 int bn_multiply_unrolled(int height, const uint32_t* a, const uint32_t* b, uint32_t* dst);
 /* Device batch of the same: nblocks blocks of 2^height words per operand. Async on `stream`. */
 int bn_multiply_unrolled_device(int height, const void* a, const void* b, void* dst, size_t nblocks, void* stream);
+/* Test hook (no reference counterpart): runs generated circuit `circuit` (0..13, the order of
+ * bitsliced_gen.hpp: bsm2_mul, bsm3_mul, bsm3x4_fma_tw, bsm3x4_mul_acc, bsm4_mul, bsm4x2_fma_tw,
+ * bsm4x2_mul_acc, bsm5_mul, bsm5_fma_tw, bsm5_mul_acc, bsm6_mul, bsm7_mul, bsm5_mul_w,
+ * bsm6_fma_w2) on the device, one 32-product block per lane, operands as that circuit
+ * documents. d_out is read first by the accumulate forms. Per-lane compact twiddles: one word per
+ * block in d_b. Wave-uniform ones (bsm5_mul_w: one word, bsm6_fma_w2: two words): one entry
+ * per 64 consecutive blocks, passed to the circuit through readfirstlane as the kernels do.
+ * Buffers must not overlap. BN_ERR_INVALID for an unknown id, a NULL pointer or more than 2^30
+ * blocks; n_blocks == 0 launches nothing. Asynchronous on `stream`. */
+int bn_circuit_device(int circuit, const void* d_a, const void* d_b, void* d_out, size_t n_blocks, void* stream);
 /* Replaces mul_binary_tower_32b_simd<HEIGHT>(a, b) (binary_tower_simd.cuh:77-127): the words as
  * 32/2^height packed GF(2^(2^height)) elements, multiplied lane by lane. 0 <= height <= 5. */
 int bn_mul_binary_tower_32b_simd(int height, uint32_t a, uint32_t b, uint32_t* out);

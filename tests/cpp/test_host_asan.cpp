@@ -8,7 +8,11 @@
 //     AdditiveNTTConf, BB31, QM31/interpolate_at) against the oracle;
 //   * the library's host-side code: the generated bitsliced circuits behind multiply_unrolled<H>,
 //     the packed-subfield helpers, bn_sumcheck_interpolate, and the argument-checking / error paths
-//     of the C-ABI (no device present here: they must fail cleanly with a status code).
+//     of the C-ABI (no device present here: they must fail cleanly with a status code);
+//   * all 14 generated circuits of csrc/bitsliced_gen.hpp, compiled into this program, through
+//     the conformance routine of circuit_conformance.hpp with a small trial count: every alias
+//     mode, every operand in a heap allocation of exactly its documented size, so a gate that
+//     indexes past an operand (the 8 shared words of bsm3x4_mul_acc's b, say) is a report.
 // Prints "ok <what>" / "FAIL <what>" per check, and "md5 ..." lines that tests/test_asan.py compares
 // with the reference's golden tables; exit status 0 iff every check passed (a sanitizer report
 // aborts the run with a non-zero status).
@@ -29,6 +33,7 @@
 #include "utils/bitslicing.hpp"
 #include "utils/common.hpp"
 #include "../../oracle/oracle.h"
+#include "circuit_conformance.hpp"
 
 static int failures = 0;
 static void check(bool ok, const char* what) {
@@ -315,6 +320,7 @@ int main() {
 	oracle_checks();
 	mirror_checks();
 	library_host_checks();
+	failures += conformance::run_all(2);
 	std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "PASSED", failures);
 	return failures ? 1 : 0;
 }

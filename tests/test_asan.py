@@ -27,7 +27,12 @@ def test_host_code_under_address_sanitizer():
     assert "ERROR: AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-5000:]
     lines = p.stdout.splitlines()
     assert not [l for l in lines if l.startswith("FAIL")]
-    assert sum(1 for l in lines if l.startswith("ok ")) >= 30
+    assert sum(1 for l in lines if l.startswith("ok ")) >= 100
+    # the generated circuits' section (circuit_conformance.hpp): every circuit, every alias mode
+    for name in ("bsm2_mul", "bsm3_mul", "bsm3x4_fma_tw", "bsm3x4_mul_acc", "bsm4_mul", "bsm4x2_fma_tw", "bsm4x2_mul_acc",
+                 "bsm5_mul", "bsm5_fma_tw", "bsm5_mul_acc", "bsm6_mul", "bsm7_mul", "bsm5_mul_w", "bsm6_fma_w2"):
+        assert any(l.startswith("ok %s random" % name) for l in lines), name
+        assert not name.endswith("_mul") or any(l.startswith("ok %s alias" % name) for l in lines), name
     with open(os.path.join(GOLDEN, "additive_ntt_md5.json")) as f:
         ntt = json.load(f)["hashes"]
     with open(os.path.join(GOLDEN, "bb31_ntt_md5.json")) as f:

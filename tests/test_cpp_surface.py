@@ -105,18 +105,15 @@ def test_cpp_prime_field_mirror_runs_reference_flows():
     assert len([l for l in out if l.startswith("ok Prime Field Sumcheck Test")]) == 3
 
 
-CIRCUITS_BIN = os.path.join(ROOT, "tests", "cpp", "build", "test_circuits")
-
-
 def test_generated_constant_operand_circuits_match_oracle():
     """bsm6_fma_w2 (the fold's scalar-challenge GF(2^64) product, sc_fold_pair), bsm5_fma_tw (the
     NTT's per-lane compact-twiddle product) and bsm5_mul_w (its scalar-twiddle top stage) run on
-    the host against the oracle's tower product (CPU)."""
-    os.makedirs(os.path.dirname(CIRCUITS_BIN), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
-                           "-I", os.path.join(ROOT, "binius-ntt_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "cpp", "test_circuits.cpp"), "-o", CIRCUITS_BIN,
-                           "-L", ORACLE, "-loracle", "-Wl,-rpath," + ORACLE])
-    p = subprocess.run([CIRCUITS_BIN], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "ok bsm6_fma_w2" in p.stdout and "ok bsm5_fma_tw" in p.stdout and "ok bsm5_mul_w" in p.stdout
+    the host against the oracle's tower product (CPU). The program is the conformance run of all
+    14 circuits, built once per session (tests/_circuits.py; tests/test_circuits.py asserts the
+    full set of its lines)."""
+    import _circuits
+    rc, lines, _, _ = _circuits.host_conformance()
+    stdout = "\n".join(lines)
+    assert rc == 0, stdout
+    assert "ok bsm6_fma_w2" in stdout and "ok bsm5_fma_tw" in stdout and "ok bsm5_mul_w" in stdout
+    assert "FAIL" not in stdout
