@@ -163,14 +163,14 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 		}
 		// the stage on the top tile bit: qu's bits 0..5 are the lane's, and when none of them moves
 		// the twiddle (twt[j][0..5] = 0: the tile's other bits are lower stages) it is the
-		// workgroup-uniform part alone, so the circuit's twiddle side is scalar (bsm5_mul_w)
+		// workgroup-uniform part alone, so the circuit's twiddle side is scalar (ntt_mul32_w)
 		bool uni = FMAX == 32 && !inw && m == kBlkBits - 1 && ps.field[j] == 32 && !(BS_DBG(P) & 4);
 #pragma unroll
 		for (int mm = 0; mm < kBlkBits - 1; mm++) uni = uni && ps.twt[j][mm] == 0u;
 		if (uni) {
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 			__builtin_amdgcn_sched_barrier(0);
-			bsm5_mul_w(V, (uint32_t)__builtin_amdgcn_readfirstlane((int)cu_w[j]), Pr);
+			ntt_mul32_w(V, (uint32_t)__builtin_amdgcn_readfirstlane((int)cu_w[j]), Pr);
 			__builtin_amdgcn_sched_barrier(0);
 		} else {
 		if (inw) {  // the bottom pass starts at stage 0: j is the stage

@@ -8,6 +8,7 @@
 
 #include "antt_bs.hpp"
 #include "bitsliced.hpp"
+#include "bitsliced_ntt_gen.hpp"
 
 namespace bn {
 
@@ -43,7 +44,7 @@ __device__ __forceinline__ void mul_tw(int field, const uint32_t* x, const uint3
 #pragma unroll
 		for (int g = 0; g < 2; g++) bsm4_mul(x + 16 * g, W, out + 16 * g);
 	} else {
-		bsm5_mul(x, W, out);
+		ntt_mul32(x, W, out);
 	}
 }
 

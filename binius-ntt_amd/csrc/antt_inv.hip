@@ -314,7 +314,7 @@ __global__ __launch_bounds__(64 * L, 2) void antt_inv_bs_pass(InvBsParams P) {
 		if (uni) {
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 			__builtin_amdgcn_sched_barrier(0);
-			bsm5_mul_w(V, (uint32_t)__builtin_amdgcn_readfirstlane((int)cu_w[j]), Pr);
+			ntt_mul32_w(V, (uint32_t)__builtin_amdgcn_readfirstlane((int)cu_w[j]), Pr);
 			__builtin_amdgcn_sched_barrier(0);
 		} else {
 #pragma unroll

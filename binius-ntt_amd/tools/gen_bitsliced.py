@@ -10,24 +10,30 @@ gate). Differences that matter on CDNA4:
 * XOR chains and AND->XOR pairs are fused into gfx950's 3-input v_bitop3_b32
   (XOR3 = 0x96, (a&b)^c = 0x6a) through __builtin_amdgcn_bitop3_b32 — hipcc does not form
   XOR3 on its own;
+* the GF(2^32) circuits of the NTT passes (a second header, bitsliced_ntt_gen.hpp) cancel what the
+  Karatsuba recombination adds twice and pack every multi-operand XOR by operand count
+  (recombine, PackedEmitter, write_ntt_header);
 * every multiplier is alias-safe (all inputs are read before any output is written).
 
 Word i of a bitsliced operand holds bit i (tower basis) of 32 independent field elements.
 Output: binius-ntt_amd/csrc/bitsliced_gen.hpp, or the file given with -o / --output (the suite
-regenerates into a temporary file and compares it with the committed header). The gate count of
+regenerates into a temporary file and compares it with the committed header), and
+bitsliced_ntt_gen.hpp beside it. The gate count of
 every circuit is printed to stderr, in the header's order.
 """
 import argparse
 import os
 import sys
 
+NTT_NAME = "bitsliced_ntt_gen.hpp"
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc", "bitsliced_gen.hpp")
 
 
 class DAG:
-    def __init__(self):
+    def __init__(self, flat=False):
         self.nodes = []  # (op, args)  op in {'in','and','xor'}
         self.index = {}
+        self.flat = flat  # recombine() with the flattened, cancelled high half (PackedEmitter's input)
 
     def node(self, op, args):
         if op == "xor":
@@ -72,6 +78,41 @@ def mul_alpha(d, a, h):
     return a1 + vadd(d, a0, mul_alpha(d, a1, h - 1))
 
 
+def alpha_terms(m):
+    """mul_alpha on m words as index sets: word i of alpha * c is the XOR of c[k], k in the i-th
+    set. The sets hold 2m - 1 indices in all, i.e. m - 1 XORs: exactly mul_alpha's count, so the
+    recursion shares nothing that the flat form would lose."""
+    if m == 1:
+        return [{0}]
+    half = m >> 1
+    sub = alpha_terms(half)
+    return [{half + i} for i in range(half)] + [{i} | {half + k for k in sub[i]} for i in range(half)]
+
+
+def recombine(d, z0, z1, z2, h):
+    """Karatsuba recombination lo = z0 + z2, hi = z1 + lo + alpha * z2 of three 2^(h-1)-word
+    partial products. On a flat DAG every word of hi is one XOR over distinct partial-product
+    words: where alpha * z2 contains z2[i] itself it cancels against lo[i]'s (in GF(4): hi = z1 +
+    z0, one XOR instead of three; one word per level above), and the remaining operands are left
+    to PackedEmitter, which packs a multi-operand XOR into 3-input instructions whatever its
+    association."""
+    m = len(z0)
+    lo = vadd(d, z0, z2)
+    if not d.flat:
+        return lo + vadd(d, vadd(d, z1, lo), mul_alpha(d, z2, h - 1))
+    hi = []
+    for i, ks in enumerate(alpha_terms(m)):
+        if i in ks:
+            terms = [z1[i], z0[i]] + [z2[k] for k in sorted(ks - {i})]
+        else:
+            terms = [z1[i], lo[i]] + [z2[k] for k in sorted(ks)]
+        x = terms[0]
+        for t in terms[1:]:
+            x = d.xor(x, t)
+        hi.append(x)
+    return lo + hi
+
+
 def karatsuba(d, a, b, h):
     """Recursive Karatsuba tower product (binary_tower.cuh:35-50), built depth-first so that
     node creation order == a low-register-pressure evaluation order."""
@@ -82,9 +123,7 @@ def karatsuba(d, a, b, h):
     z0 = karatsuba(d, a0, b0, h - 1)
     z2 = karatsuba(d, a1, b1, h - 1)
     z1 = karatsuba(d, vadd(d, a0, a1), vadd(d, b0, b1), h - 1)
-    lo = vadd(d, z0, z2)
-    hi = vadd(d, vadd(d, z1, lo), mul_alpha(d, z2, h - 1))
-    return lo + hi
+    return recombine(d, z0, z1, z2, h)
 
 
 class Emitter:
@@ -175,6 +214,109 @@ class Emitter:
                 lines.append("BN_SCHED_BARRIER();")
         for lv, r in outputs:
             lines.append("%s = %s;" % (lv, "0u" if r is None else nm(r)))
+        return lines
+
+
+class PackedEmitter(Emitter):
+    """Emitter that packs by operand count instead of by the DAG's association. A maximal tree of
+    single-use XOR nodes is one multi-operand XOR; its operands are values (anything with several
+    uses, inputs) and single-use ANDs. p values and j ANDs cost j + ceil((p - 1) / 2) instructions
+    (an AND-XOR per AND, XOR3s, at most one 2-input XOR), where the pairwise fusion of Emitter
+    stops at every node that is already fused. Instructions are issued as soon as their operands
+    exist, at the DAG position of the inner node that brings them in, so the depth-first order
+    (and with it the live ranges) is the one Emitter gives.
+
+    Two values that wait for a third keep two registers where their XOR keeps one. When the next
+    operand of their multi-operand XOR is more than FLUSH_GAP DAG positions away (the words of a
+    half-size partial product, which wait for the level above), they are combined at once, at
+    the price of one instruction where the operand count was odd: GF(2^32) 937 -> 941 gates, and
+    the pass kernels compile without spills (at 937: 12 spilled registers in the bottom pass)."""
+
+    FLUSH_GAP = 320
+
+    def emit(self, input_map, outputs, barrier_every=0):
+        d = self.d
+        live = set()
+        stack = [r for _, r in outputs if r is not None]
+        while stack:
+            n = stack.pop()
+            if n in live:
+                continue
+            live.add(n)
+            op, args = d.nodes[n]
+            if op != "in":
+                stack.extend(args)
+        order = sorted(live)
+        # a single-use XOR or AND whose one consumer is an XOR is folded into that consumer
+        consumer = {}
+        for n in order:
+            op, args = d.nodes[n]
+            if op == "xor":
+                for a in args:
+                    if self.uses[a] == 1 and d.nodes[a][0] in ("xor", "and"):
+                        consumer[a] = n
+
+        def root(n):
+            while n in consumer:
+                n = consumer[n]
+            return n
+        lines = []
+        name = {}
+        cnt = [0]
+        pending = {}  # root -> ([value names], [(a, b) of folded ANDs])
+
+        def gate(expr):
+            v = "t%d" % cnt[0]
+            cnt[0] += 1
+            lines.append("const uint32_t %s = %s;" % (v, expr))
+            if barrier_every and cnt[0] % barrier_every == 0:
+                lines.append("BN_SCHED_BARRIER();")
+            return v
+
+        def drain(vals, ands):
+            while True:
+                if ands and vals:
+                    a, b = ands.pop(0)
+                    vals[0] = gate("BN_ANDXOR(%s, %s, %s)" % (a, b, vals[0]))
+                elif len(vals) >= 3:
+                    vals[:3] = [gate("BN_XOR3(%s, %s, %s)" % tuple(vals[:3]))]
+                else:
+                    return
+
+        for n in order:
+            op, args = d.nodes[n]
+            if op == "in":
+                name[n] = input_map[args[0]]
+            elif op == "xor":
+                r = root(n)
+                vals, ands = pending.setdefault(r, ([], []))
+                for a in args:
+                    if a not in consumer:
+                        vals.append(name[a])
+                    elif d.nodes[a][0] == "and":
+                        ands.append(tuple(name[x] for x in d.nodes[a][1]))
+                drain(vals, ands)
+                if r != n and self.FLUSH_GAP and len(vals) == 2 and consumer[n] - n > self.FLUSH_GAP:
+                    vals[:] = [gate("%s ^ %s" % tuple(vals))]
+                if r == n:
+                    if not vals:
+                        vals.append(gate("%s & %s" % ands.pop(0)))
+                        drain(vals, ands)
+                    if len(vals) == 2:
+                        vals[:] = [gate("%s ^ %s" % tuple(vals))]
+                    name[n] = vals[0]
+                    del pending[r]
+            elif n in consumer:
+                continue
+            elif op.startswith("csum:"):
+                name[n] = gate("%s ^ (%s >> %s)" % (name[args[0]], name[args[0]], op[5:]))
+            elif op.startswith("wleaf:"):
+                name[n] = gate("BN_BIT(%s, %s)" % (name[args[0]], op[6:]))
+            else:
+                name[n] = gate("%s & %s" % (name[args[0]], name[args[1]]))
+        assert not pending
+        for lv, r in outputs:
+            lines.append("%s = %s;" % (lv, "0u" if r is None else name[r]))
         return lines
 
 
@@ -524,7 +666,10 @@ def make_emitter(dag, roots, low_pressure=False):
     """auto: XOR3 / AND-XOR fusion (Emitter) for the circuits that run inside register-hungry
     kernels (the full GF(2^8..2^32) multiplies of the NTT passes and the sumcheck's quad product:
     the LUT cover re-derives nodes and reorders, and there it costs more in spills than it saves in
-    gates — c4 d=3 4.5 -> 6.0 ms measured), the LUT mapping everywhere else."""
+    gates — c4 d=3 4.5 -> 6.0 ms measured), the LUT mapping everywhere else. A flat DAG
+    gets PackedEmitter, which keeps Emitter's order."""
+    if dag.flat and low_pressure and EMITTER == "auto":
+        return PackedEmitter(dag, roots)
     if EMITTER == "lut" or (EMITTER == "auto" and not low_pressure):
         return LutEmitter(dag, roots)
     return Emitter(dag, roots)
@@ -541,10 +686,10 @@ W2_BARRIER_EVERY = int(os.environ.get("BN_GEN_W2_BARRIER_EVERY", "32"))
 W2_LUT = int(os.environ.get("BN_GEN_W2_LUT", "1"))
 
 
-def gen_full(h):
+def gen_full(h, packed=False):
     """out = a * b, both bitsliced, alias-safe (every input word is read before any output word is
     written)."""
-    d = DAG()
+    d = DAG(packed)
     n = 1 << h
     a = [d.inp("a%d" % i) for i in range(n)]
     b = [d.inp("b%d" % i) for i in range(n)]
@@ -576,9 +721,7 @@ def kara_w(d, a, cid, off, h):
         z1 = [d.and_(d.xor(a0[0], a1[0]), wsum)]
     else:
         z1 = kara_w(d, vadd(d, a0, a1), d.node("csum:%d" % half, (cid,)), off, h - 1)
-    lo = vadd(d, z0, z2)
-    hi = vadd(d, vadd(d, z1, lo), mul_alpha(d, z2, h - 1))
-    return lo + hi
+    return recombine(d, z0, z1, z2, h)
 
 
 def kara_w_multi(d, aa, cid, off, h):
@@ -597,12 +740,7 @@ def kara_w_multi(d, aa, cid, off, h):
         z1 = [[d.and_(d.xor(a[0], a[1]), wsum)] for a in aa]
     else:
         z1 = kara_w_multi(d, [vadd(d, a[:half], a[half:]) for a in aa], d.node("csum:%d" % half, (cid,)), off, h - 1)
-    out = []
-    for k in range(len(aa)):
-        lo = vadd(d, z0[k], z2[k])
-        hi = vadd(d, vadd(d, z1[k], lo), mul_alpha(d, z2[k], h - 1))
-        out.append(lo + hi)
-    return out
+    return [recombine(d, z0[k], z1[k], z2[k], h) for k in range(len(aa))]
 
 
 def gen_fma_tw_multi(h, cnt):
@@ -641,12 +779,7 @@ def kara_multi(d, aa, b, h):
     z0 = kara_multi(d, [a[:half] for a in aa], b[:half], h - 1)
     z2 = kara_multi(d, [a[half:] for a in aa], b[half:], h - 1)
     z1 = kara_multi(d, [vadd(d, a[:half], a[half:]) for a in aa], vadd(d, b[:half], b[half:]), h - 1)
-    out = []
-    for k in range(len(aa)):
-        lo = vadd(d, z0[k], z2[k])
-        hi = vadd(d, vadd(d, z1[k], lo), mul_alpha(d, z2[k], h - 1))
-        out.append(lo + hi)
-    return out
+    return [recombine(d, z0[k], z1[k], z2[k], h) for k in range(len(aa))]
 
 
 def gen_acc_multi(h, cnt):
@@ -727,17 +860,17 @@ def gen_fma_w2():
     return e.emit(imap, [("out[%d]" % i, o[i]) for i in range(n)], W2_BARRIER_EVERY)
 
 
-def gen_mul_w(h):
+def gen_mul_w(h, packed=False):
     """out = a * w in GF(2^(2^h)), w compact and wave-uniform (the NTT's top block stage of a tile,
     whose twiddle depends on no tile bit): the twiddle side is scalar work as in gen_fma_w2."""
-    d = DAG()
+    d = DAG(packed)
     n = 1 << h
     a = [d.inp("a%d" % i) for i in range(n)]
     w = d.inp("w")
     res = kara_w(d, a, w, 0, h)
     imap = {"a%d" % i: "a[%d]" % i for i in range(n)}
     imap["w"] = "w"
-    e = ScalarLutEmitter(d, res, ("w",))
+    e = PackedEmitter(d, res) if packed else ScalarLutEmitter(d, res, ("w",))
     return e.emit(imap, [("out[%d]" % i, res[i]) for i in range(n)], W2_BARRIER_EVERY)
 
 
@@ -775,7 +908,11 @@ def fn(sig, lines):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("-o", "--output", default=OUT, help="file to write (default: %(default)s)")
-    out_path = ap.parse_args(argv).output
+    ap.add_argument("--ntt-output", default=None,
+                    help="the NTT passes' header (default: %s beside the file given with -o)" % NTT_NAME)
+    args = ap.parse_args(argv)
+    out_path = args.output
+    ntt_path = args.ntt_output or os.path.join(os.path.dirname(os.path.abspath(out_path)), NTT_NAME)
     parts = ["// GENERATED by binius-ntt_amd/tools/gen_bitsliced.py -- do not edit.",
              "// Bitsliced binary-tower multipliers (Karatsuba tower, gfx950 v_bitop3 fusion).",
              "#pragma once", "#include <hip/hip_runtime.h>", "#include <stdint.h>", "",
@@ -840,6 +977,32 @@ def main(argv=None):
         f.write("\n".join(parts) + "\n")
     for s in stats:
         print(s, file=sys.stderr)
+    write_ntt_header(ntt_path)
+
+
+def write_ntt_header(path):
+    """The second header: the two GF(2^32) circuits of the NTT passes (mul_tw and the scalar top
+    stage), built flat and emitted by PackedEmitter. They are variants of bsm5_mul and bsm5_mul_w,
+    which keep their form in the first header for their other consumers. Their instruction counts
+    go to stderr as `ntt <name> <count>`."""
+    parts = ["// GENERATED by binius-ntt_amd/tools/gen_bitsliced.py -- do not edit.",
+             "// The additive NTT passes' GF(2^32) multipliers: the Karatsuba tower of bitsliced_gen.hpp with",
+             "// the recombination's double additions cancelled and every multi-operand XOR packed by",
+             "// operand count (recombine, PackedEmitter).",
+             "#pragma once", '#include "bitsliced_gen.hpp"', "", "namespace bn {", ""]
+    ml = gen_full(5, True)
+    wl = gen_mul_w(5, True)
+    for name, what, sig, lines in (
+            ("ntt_mul32", "out = a * b for 32 bitsliced GF(2^32) products, alias-safe as bsm5_mul",
+             "const uint32_t* a, const uint32_t* b, uint32_t* out", ml),
+            ("ntt_mul32_w", "out = a * w, w compact and wave-uniform as for bsm5_mul_w; out must not alias a",
+             "const uint32_t* __restrict__ a, uint32_t w, uint32_t* __restrict__ out", wl)):
+        parts.append("/* %s: %s; %d instructions */" % (name, what, count_ops(lines)))
+        parts.append("__host__ __device__ __forceinline__ void %s(%s) {\n\t" % (name, sig) + "\n\t".join(lines) + "\n}\n")
+        print("ntt %s %d" % (name, count_ops(lines)), file=sys.stderr)
+    parts.append("}  // namespace bn")
+    with open(path, "w") as f:
+        f.write("\n".join(parts) + "\n")
 
 
 if __name__ == "__main__":
