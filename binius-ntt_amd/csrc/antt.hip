@@ -1,6 +1,6 @@
 // Additive NTT over GF(2^32) / GF(2^128): plan management, C-ABI entry points and the
-// v0 (correctness-first, compact-layout) kernel. The bitsliced fast path lives in
-// antt_bs.hip and is selected by bn_antt_forward_device when it supports the plan.
+// v0 (correctness-first, compact-layout) kernel of both directions. The bitsliced fast path lives
+// in antt_bs.hip (forward) and antt_inv.hip (inverse) and is selected when it supports the plan.
 //
 // Semantics (src/ulvt/ntt/additive_ntt.cuh): for each coset c < 2^log_rate the input is
 // copied and butterflies u += w v ; v += u run for stage = log_h-1 .. 0 over blocks of
@@ -45,33 +45,37 @@ void subspace_evals(int log_h, int log_rate, std::vector<uint32_t>& s) {
 }
 
 // ------------------------------------------------------------------------------------
-// v0 kernel: one launch per group of up to kMaxGroup stages. A workgroup owns a tile of
+// v0 kernel: one launch per group of up to kTileLog stages. A workgroup owns a tile of
 // 2^(k+c) elements: the k group bits [lo, lo+k) plus the c lowest index bits (so that
 // each group of 2^c consecutive elements is read contiguously). Elements are staged in
 // LDS; each thread walks its butterflies stage by stage.
+// Both directions (INV: the inverse transform, antt_inv.hip): the forward runs the stages of a
+// group downward over every coset block of the output; the inverse runs them upward with the
+// butterfly undone (v += u ; u += w v, the same twiddle) over the one coset block it is given.
 // ------------------------------------------------------------------------------------
 constexpr int kTileLog = 12;  // 4096 elements; 64 KiB at 16 B/element
 
 struct V0Params {
-	const uint32_t* src;  // group input (d_in for the first group: coset copies are implicit)
+	const uint32_t* src;  // the caller's input (the forward's is shared by every coset)
 	uint32_t* dst;        // d_out
 	const uint32_t* s;    // subspace table, log_h x width
 	int width;
 	int log_h;
 	int log_rate;
 	int lo, k, c;
-	int first;  // 1: src is the shared input (same for every coset), else src == dst
+	int first;  // 1: the first group of the transform reads src, every other runs in place in dst
+	int coset;  // inverse: the coset of the input block (the forward takes it from the block index)
 };
 
-template <int L>
+template <int L, bool INV>
 __global__ __launch_bounds__(256) void antt_v0_group(V0Params p) {
 	extern __shared__ uint32_t lds[];
 	const int tile_log = p.k + p.c;
 	const int tile = 1 << tile_log;
 	const int outer_log = p.log_h - tile_log;
 	const size_t n = (size_t)1 << p.log_h;
-	const int coset = (int)(blockIdx.x >> outer_log);
-	const size_t rest = blockIdx.x & (((size_t)1 << outer_log) - 1);
+	const int coset = INV ? p.coset : (int)(blockIdx.x >> outer_log);
+	const size_t rest = INV ? blockIdx.x : blockIdx.x & (((size_t)1 << outer_log) - 1);
 	const int mid_bits = p.lo - p.c;
 	const size_t o_mid = rest & (((size_t)1 << mid_bits) - 1);
 	const size_t o_hi = rest >> mid_bits;
@@ -80,8 +84,8 @@ __global__ __launch_bounds__(256) void antt_v0_group(V0Params p) {
 		const size_t g = (size_t)pos >> p.c;
 		return (o_hi << (p.lo + p.k)) | (g << p.lo) | (o_mid << p.c) | cc;
 	};
-	const uint32_t* src = p.first ? p.src : (p.dst + (size_t)coset * n * L);
-	uint32_t* dst = p.dst + (size_t)coset * n * L;
+	uint32_t* dst = INV ? p.dst : p.dst + (size_t)coset * n * L;
+	const uint32_t* src = p.first ? p.src : dst;
 
 	uint8_t* tab = (uint8_t*)(lds + (size_t)tile * L);  // GF(2^8) log/exp tables after the tile
 	gf8_tables_to_lds(tab);
@@ -92,7 +96,8 @@ __global__ __launch_bounds__(256) void antt_v0_group(V0Params p) {
 	}
 	__syncthreads();
 
-	for (int stage = p.lo + p.k - 1; stage >= p.lo; stage--) {
+	for (int i = 0; i < p.k; i++) {
+		const int stage = INV ? p.lo + i : p.lo + p.k - 1 - i;
 		const int b = stage - p.lo + p.c;
 		const int npairs = tile >> 1;
 		const uint32_t* srow = p.s + (size_t)stage * p.width;
@@ -108,8 +113,9 @@ __global__ __launch_bounds__(256) void antt_v0_group(V0Params p) {
 #pragma unroll
 			for (int l = 0; l < L; l++) {
 				uint32_t u = lds[pu * L + l], v = lds[pv * L + l];
+				if (INV) v ^= u;
 				u ^= (uint32_t)dmul_t<5>(w, v, tab);
-				v ^= u;
+				if (!INV) v ^= u;
 				lds[pu * L + l] = u;
 				lds[pv * L + l] = v;
 			}
@@ -171,48 +177,39 @@ static int timing_resolve(bn_antt_plan* p) {
 	return BN_OK;
 }
 
-int launch_v0(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, hipStream_t st) {
+// One transform on the compact kernel. The groups are balanced (an unbalanced tail would launch
+// 2-point tiles): the forward takes them from the top stages down, the inverse the same list reversed.
+static int launch_v0(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, bool inv, int coset, hipStream_t st) {
 	const int log_h = plan->log_h;
 	const int L = plan->limbs;
-	int hi = log_h;
-	bool first = true;
-	int kind = 0;
-	// balanced passes of <= kTileLog stages (an unbalanced tail would launch 2-point tiles)
 	const int passes = (log_h + kTileLog - 1) / kTileLog;
-	while (hi > 0) {
-		const int k = (hi + (passes - kind) - 1) / (passes - kind);
-		const int lo = hi - k;
+	std::vector<std::pair<int, int>> groups;  // (lo, k)
+	for (int hi = log_h, i = 0; hi > 0; i++) {
+		const int k = (hi + (passes - i) - 1) / (passes - i);
+		groups.push_back({hi - k, k});
+		hi -= k;
+	}
+	if (inv) std::reverse(groups.begin(), groups.end());
+	const void* fn = L == 4 ? (inv ? (const void*)antt_v0_group<4, true> : (const void*)antt_v0_group<4, false>)
+	                        : (inv ? (const void*)antt_v0_group<1, true> : (const void*)antt_v0_group<1, false>);
+	for (size_t i = 0; i < groups.size(); i++) {
+		const int lo = groups[i].first, k = groups[i].second;
 		const int c = std::min(lo, kTileLog - k);
-		V0Params p{d_in, d_out, plan->s_dev, plan->width, log_h, plan->log_rate, lo, k, c, first ? 1 : 0};
-		const size_t blocks = ((size_t)1 << (log_h - k - c)) << plan->log_rate;
+		V0Params p{d_in, d_out, plan->s_dev, plan->width, log_h, plan->log_rate, lo, k, c, i == 0 ? 1 : 0, coset};
+		// the forward writes every coset block, the inverse one block of n elements
+		const size_t blocks = ((size_t)1 << (log_h - k - c)) << (inv ? 0 : plan->log_rate);
 		const size_t lds = ((size_t)1 << (k + c)) * L * sizeof(uint32_t) + kGf8LdsBytes;
-		const void* fn = L == 4 ? (const void*)antt_v0_group<4> : (const void*)antt_v0_group<1>;
 		BN_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		int rc = timing_begin(plan, kind, st);
+		// per-launch timing is the forward's (bench.py)
+		int rc = inv ? BN_OK : timing_begin(plan, (int)i, st);
 		if (rc != BN_OK) return rc;
-		if (L == 4)
-			hipLaunchKernelGGL(antt_v0_group<4>, dim3((unsigned)blocks), dim3(256), lds, st, p);
-		else
-			hipLaunchKernelGGL(antt_v0_group<1>, dim3((unsigned)blocks), dim3(256), lds, st, p);
-		BN_HIP(hipGetLastError());
-		rc = timing_end(plan, kind, st);
+		void* args[] = {&p};
+		BN_HIP(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), args, lds, st));
+		rc = inv ? BN_OK : timing_end(plan, (int)i, st);
 		if (rc != BN_OK) return rc;
-		kind++;
-		first = false;
-		hi = lo;
 	}
 	return BN_OK;
 }
-
-// Bitsliced fast path (antt_bs.hip, antt_rr.hip), used when bs_supports(plan).
-int launch_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st);
-bool bs_supports(const bn_antt_plan* plan);
-int bs_prepare(bn_antt_plan* plan);
-int bs_time_passes(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, int reps,
-                   hipStream_t st, float* ms, int max_passes, int* n_out);
-// Inverse transform (antt_inv.hip): compact tiles for variant 0, bitsliced LDS tiles otherwise.
-int launch_inv_v0(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, int coset, hipStream_t st);
-int launch_inv_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, int coset, size_t batch, hipStream_t st);
 
 // Kernel variants: 0 compact tiles (log_h < 12), 1 bitsliced LDS tiles (antt_bs_pass), 4 bitsliced
 // register tiles (antt_rr_pass), 5 = 4 for the passes whose twiddles all lie in GF(2^8) and 1 for
@@ -307,7 +304,7 @@ static int forward_device_impl(bn_antt_plan* p, const void* d_in, void* d_out, s
 	const size_t n_out = n_in << p->log_rate;
 	if (p->variant != 0) return launch_bs(p, (const uint32_t*)d_in, (uint32_t*)d_out, batch, st);
 	for (size_t b = 0; b < batch; b++) {
-		int rc = launch_v0(p, (const uint32_t*)d_in + b * n_in, (uint32_t*)d_out + b * n_out, st);
+		int rc = launch_v0(p, (const uint32_t*)d_in + b * n_in, (uint32_t*)d_out + b * n_out, false, 0, st);
 		if (rc != BN_OK) return rc;
 	}
 	return BN_OK;
@@ -361,7 +358,7 @@ static int inverse_device_impl(bn_antt_plan* p, const void* d_in, void* d_out, i
 	if (p->variant != 0) return launch_inv_bs(p, (const uint32_t*)d_in, (uint32_t*)d_out, coset, batch, st);
 	const size_t n_words = ((size_t)1 << p->log_h) * p->limbs;
 	for (size_t b = 0; b < batch; b++) {
-		int rc = launch_inv_v0(p, (const uint32_t*)d_in + b * n_words, (uint32_t*)d_out + b * n_words, coset, st);
+		int rc = launch_v0(p, (const uint32_t*)d_in + b * n_words, (uint32_t*)d_out + b * n_words, true, coset, st);
 		if (rc != BN_OK) return rc;
 	}
 	return BN_OK;

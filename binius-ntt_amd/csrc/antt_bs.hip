@@ -89,51 +89,28 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 		return __builtin_amdgcn_s_memtime();
 	};
 
-	auto tile_off = [&](int q) -> size_t {
-		size_t off = 0;
-#pragma unroll
-		for (int m = 0; m < kBlkBits; m++) off |= (size_t)((q >> m) & 1) << ps.bb[m];
-		return off;
-	};
 	// tile -> (outer bits, coset, batch) -> addresses
-	const size_t tile = blockIdx.x;
-	const size_t outer = tile & (((size_t)1 << ps.n_outer) - 1);
-	const size_t rest = tile >> ps.n_outer;
-	const int coset = (int)(rest & ((1u << P.log_rate) - 1));
-	const size_t batch = rest >> P.log_rate;
-	size_t outer_off = 0;
-	for (int m = 0; m < ps.n_outer; m++) outer_off |= ((outer >> m) & 1) << ps.ob[m];
-	uint32_t* const dst = P.dst + (((batch << P.log_rate) + (size_t)coset) * n) * L;
-	const uint32_t* const src = IN_COMPACT ? (P.src + batch * n * L) : dst;
-	// the tile's global loads, all in flight at once
+	const TileAddr ta = tile_addr(ps, P.log_rate);
+	const size_t outer_off = ta.outer_off;
+	uint32_t* const dst = P.dst + (((ta.batch << P.log_rate) + (size_t)ta.coset) * n) * L;
+	const uint32_t* const src = IN_COMPACT ? (P.src + ta.batch * n * L) : dst;
+	// the tile's global loads, all in flight at once. Bottom pass: bb[m] = 5 + m (bs_prepare checks
+	// it), the tile is one contiguous run of 2^12 elements at outer_off: a workgroup-uniform base and
+	// a 32-bit offset per lane
 	uint4 gbuf[kLoads];
-	auto issue = [&](const uint32_t* s, size_t ooff) {
-		// bottom pass: bb[m] = 5 + m (bs_prepare checks it), the tile is one contiguous run of
-		// 2^12 elements at ooff: a workgroup-uniform base and a 32-bit offset per lane
-		const uint32_t* const s0 = s + ooff * L;
+	auto issue = [&]() {
+		if (IN_COMPACT) {
+			const uint32_t* const s0 = src + outer_off * L;
 #pragma unroll
-		for (int r = 0; r < kLoads; r++) {
-			if (IN_COMPACT) {
-				// compact elements: 16-byte loads, 8*L lanes per 32-element block
+			for (int r = 0; r < kLoads; r++) {
 				const int u = tid + r * NT;
-				const int q = u / (8 * L), j = u % (8 * L);
-				const uint32_t* g = LAST ? s0 + (uint32_t)(4 * u) : s + (ooff | tile_off(q)) * L + 4 * j;
-				gbuf[r] = (BS_DBG(P) & 1) ? make_uint4(u, j, q, tid) : ld_stream(g);
-			} else {
-				// bitsliced: limb l of block q is 128 contiguous bytes, each wave loads its own plane
-				const int u = lane + r * 64;
-				const int q = u >> 3, j = u & 7;
-				const uint32_t* g = LAST ? s0 + (uint32_t)(q * 32 * L + 32 * l + 4 * j) : s + (ooff | tile_off(q)) * L + 32 * l + 4 * j;
-				gbuf[r] = (BS_DBG(P) & 1) ? make_uint4(u, j, q, tid) : ld_stream(g);
+				const uint32_t* g = LAST ? s0 + (uint32_t)(4 * u) : src + compact_off<L>(ps, outer_off, u);
+				gbuf[r] = (BS_DBG(P) & 1) ? make_uint4(u, u % (8 * L), u / (8 * L), tid) : ld_stream(g);
 			}
-		}
-	};
-
-	auto tile_tw = [&](int j, int q) -> uint32_t {
-		uint32_t w = 0;
+		} else {
 #pragma unroll
-		for (int m = 0; m < kBlkBits; m++) w ^= ps.twt[j][m] & (uint32_t)__builtin_amdgcn_sbfe(q, m, 1);
-		return w;
+			for (int r = 0; r < kLoads; r++) gbuf[r] = load_plane_bitsliced<L, LAST>(ps, src, outer_off, l, lane, r, BS_DBG(P) & 1);
+		}
 	};
 
 	// ---- tile-bit stages (index bits >= 5), high to low. Lane = block pair of the wave's limb;
@@ -150,7 +127,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 		const int m = inw ? kBlkBits - 1 : ps.stage_m[j];
 		const int qu = ((pair >> m) << (m + 1)) | (pair & ((1 << m) - 1));
 		const int qv = qu | (1 << m);
-		const uint32_t w = cu_w[j] ^ tile_tw(j, qu);
+		const uint32_t w = cu_w[j] ^ tile_tw(ps, j, qu);
 		uint32_t* pu = plane + qu * kLimbStride;
 		uint32_t* pv = plane + qv * kLimbStride;
 		uint32_t W[32], V[32], Pr[32], U[32];
@@ -161,24 +138,22 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 #pragma unroll
 			for (int i = 0; i < 32; i += 4) *(uint4*)(U + i) = *(const uint4*)(pu + i);
 		}
-		// the stage on the top tile bit: qu's bits 0..5 are the lane's, and when none of them moves
-		// the twiddle (twt[j][0..5] = 0: the tile's other bits are lower stages) it is the
-		// workgroup-uniform part alone, so the circuit's twiddle side is scalar (ntt_mul32_w)
-		bool uni = FMAX == 32 && !inw && m == kBlkBits - 1 && ps.field[j] == 32 && !(BS_DBG(P) & 4);
-#pragma unroll
-		for (int mm = 0; mm < kBlkBits - 1; mm++) uni = uni && ps.twt[j][mm] == 0u;
+		// the stage on the top tile bit with a lane-independent twiddle: scalar twiddle side
+		const bool uni = top_stage_uniform<FMAX>(ps, j, m) && !inw && !(BS_DBG(P) & 4);
 		if (uni) {
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 			__builtin_amdgcn_sched_barrier(0);
 			ntt_mul32_w(V, (uint32_t)__builtin_amdgcn_readfirstlane((int)cu_w[j]), Pr);
 			__builtin_amdgcn_sched_barrier(0);
 		} else {
-		if (inw) {  // the bottom pass starts at stage 0: j is the stage
+		if (inw) {
+			// the bottom pass starts at stage 0: j is the stage (tw_words(w, ps.pat2[j], W) written out:
+			// through the call the GF(2^8) bottom pass at L = 1 takes 129 VGPRs against 128 and loses a
+			// wave of occupancy)
 #pragma unroll
 			for (int i = 0; i < 32; i++) W[i] = ps.pat2[j][i] ^ (uint32_t)__builtin_amdgcn_sbfe(w, i, 1);
 		} else {
-#pragma unroll
-			for (int i = 0; i < 32; i++) W[i] = (uint32_t)__builtin_amdgcn_sbfe(w, i, 1);
+			tw_words(w, nullptr, W);
 		}
 		if (TRB) {
 			const unsigned long long t = ts();
@@ -262,48 +237,29 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 	};
 
 	unsigned long long t0 = TR ? ts() : 0;
-	issue(src, outer_off);
+	issue();
 
 	// workgroup-uniform twiddle part of every stage (outer + coset bits), one lane per stage
-	if (lane < ps.k) {
-		uint32_t c = 0;
-		for (int m = 0; m < ps.n_outer; m++) c ^= ps.two[lane][m] & (0u - (uint32_t)((outer >> m) & 1));
-		for (int b = 0; b < P.log_rate; b++) c ^= ps.twc[lane][b] & (0u - (uint32_t)((coset >> b) & 1));
-		cu_w[lane] = c;
-	}
+	if (lane < ps.k) cu_w[lane] = uniform_tw(ps, lane, ta.outer, ta.coset, P.log_rate);
 
 	// ---- tile into LDS
+	if (IN_COMPACT) {
+		// split by limb into the planes, then per-(block, limb) 32x32 transposes of this wave's plane
+		// (compact_to_planes written out: through the call the single-pass GF(2^8) kernel at L = 1
+		// takes 99 VGPRs against 95 and loses a wave of occupancy)
 #pragma unroll
-	for (int r = 0; r < kLoads; r++) {
-		const uint4 g = gbuf[r];
-		if (IN_COMPACT) {
-			// split by limb into the planes
+		for (int r = 0; r < kLoads; r++) {
+			const uint4 g = gbuf[r];
 			const int u = tid + r * NT;
 			const int q = u / (8 * L), j = u % (8 * L);
 			const uint32_t w[4] = {g.x, g.y, g.z, g.w};
 #pragma unroll
-			for (int t = 0; t < 4; t++) {
-				const int word = 4 * j + t;
-				lds[(word % L) * kPlane + q * kLimbStride + word / L] = w[t];
-			}
-		} else {
-			const int u = lane + r * 64;
-			const int q = u >> 3, j = u & 7;
-			*(uint4*)(plane + q * kLimbStride + 4 * j) = g;
+			for (int t = 0; t < 4; t++) *plane_word<L>(lds, q, 4 * j + t) = w[t];
 		}
-	}
-	if (IN_COMPACT) {
-		// per-(block, limb) 32x32 transposes of this wave's plane
 		__syncthreads();
-		for (int q = lane; q < kTileBlocks; q += 64) {
-			uint32_t* x = plane + q * kLimbStride;
-			uint32_t r[32];
-#pragma unroll
-			for (int i = 0; i < 32; i += 4) *(uint4*)(r + i) = *(const uint4*)(x + i);
-			transpose32(r);
-#pragma unroll
-			for (int i = 0; i < 32; i += 4) *(uint4*)(x + i) = *(const uint4*)(r + i);
-		}
+		for (int q = lane; q < kTileBlocks; q += 64) transpose_block(plane + q * kLimbStride);
+	} else {
+		plane_from_regs(plane, lane, gbuf);
 	}
 	wave_lds_sync();
 	unsigned long long t1 = 0;
@@ -360,7 +316,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 				// shift count and lane mask as VGPR operands (an SGPR operand halves the issue rate)
 				const uint32_t d = vgpr(1u << s);
 				const uint32_t um = vgpr(~lane_mask(s));  // u-lanes (bit s clear)
-				const uint32_t cb = cu_w[s] ^ tile_tw(s, qb);
+				const uint32_t cb = cu_w[s] ^ tile_tw(ps, s, qb);
 				uint32_t W[32], T[32];
 #pragma unroll
 				for (int i = 0; i < 32; i += 4) {
@@ -372,8 +328,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 				}
 				// twiddle word i: pattern (bit-lane bits s+1..4) ^ block part, cb on B's lanes and
 				// ca = cb ^ twt[s][6] on A's (um) lanes; the host folds the um & twt[s][6] part into pat
-#pragma unroll
-				for (int i = 0; i < 32; i++) W[i] = ps.pat[s][i] ^ (uint32_t)__builtin_amdgcn_sbfe(cb, i, 1);
+				tw_words(cb, ps.pat[s], W);
 				if (BS_DBG(P) & 4) {
 #pragma unroll
 					for (int i = 0; i < 32; i++) T[i] ^= W[i];
@@ -402,16 +357,8 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 				}
 			}
 			// canonical blocks back to compact words
-#pragma unroll
-			for (int h = 0; h < 2; h++) {
-				uint32_t* x = h ? pb : pa;
-				uint32_t r[32];
-#pragma unroll
-				for (int i = 0; i < 32; i += 4) *(uint4*)(r + i) = *(const uint4*)(x + i);
-				transpose32(r);
-#pragma unroll
-				for (int i = 0; i < 32; i += 4) *(uint4*)(x + i) = *(const uint4*)(r + i);
-			}
+			transpose_block(pa);
+			transpose_block(pb);
 		}
 		if (TR) {
 			const unsigned long long t = ts();
@@ -429,10 +376,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 		const int q0 = tid / (8 * L), j0 = tid % (8 * L);
 		const uint32_t* sp[4];
 #pragma unroll
-		for (int t = 0; t < 4; t++) {
-			const int word = 4 * j0 + t;
-			sp[t] = lds + (word % L) * kPlane + q0 * kLimbStride + word / L;
-		}
+		for (int t = 0; t < 4; t++) sp[t] = plane_word<L>(lds, q0, 4 * j0 + t);
 		constexpr int kStoreIters = kTileBlocks * 8 * L / NT;  // 16
 		constexpr int kStepBlocks = NT / (8 * L);              // 8
 #pragma unroll
@@ -443,13 +387,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 			if (!(BS_DBG(P) & 2)) st_stream(g0 + (uint32_t)(4 * (tid + it * NT)), make_uint4(w[0], w[1], w[2], w[3]));
 		}
 	} else {
-#pragma unroll 4
-		for (int r = 0; r < kTileBlocks * 8 / 64; r++) {
-			const int u = lane + r * 64;
-			const int q = u >> 3, j = u & 7;
-			const uint4 g = *(const uint4*)(plane + q * kLimbStride + 4 * j);
-			if (!(BS_DBG(P) & 2)) st_stream(dst + (outer_off | tile_off(q)) * L + 32 * l + 4 * j, g);
-		}
+		store_plane_bitsliced<L>(ps, dst, outer_off, l, lane, plane, BS_DBG(P) & 2);
 	}
 	if (TR) {
 		tr[3] += ts() - t1;
@@ -506,28 +444,12 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 	const int l = w & 3, half = w >> 2;  // limb plane, product half
 	uint32_t* const cu_w = lds + 8 * kPlane;  // workgroup-uniform twiddle part per stage
 	const size_t n = (size_t)1 << P.log_h;
-	auto tile_off = [&](int q) -> size_t {
-		size_t off = 0;
-#pragma unroll
-		for (int m = 0; m < kBlkBits; m++) off |= (size_t)((q >> m) & 1) << ps.bb[m];
-		return off;
-	};
-	const size_t tile = blockIdx.x;
-	const size_t outer = tile & (((size_t)1 << ps.n_outer) - 1);
-	const size_t rest = tile >> ps.n_outer;
-	const int coset = (int)(rest & ((1u << P.log_rate) - 1));
-	const size_t batch = rest >> P.log_rate;
-	size_t ooff = 0;
-	for (int m = 0; m < ps.n_outer; m++) ooff |= ((outer >> m) & 1) << ps.ob[m];
-	uint32_t* dst = P.dst + (((batch << P.log_rate) + (size_t)coset) * n) * L;
-	const uint32_t* src = IN_COMPACT ? (P.src + batch * n * L) : dst;
+	const TileAddr ta = tile_addr(ps, P.log_rate);
+	const size_t ooff = ta.outer_off;
+	uint32_t* dst = P.dst + (((ta.batch << P.log_rate) + (size_t)ta.coset) * n) * L;
+	const uint32_t* src = IN_COMPACT ? (P.src + ta.batch * n * L) : dst;
 
-	if (tid < ps.k) {
-		uint32_t c = 0;
-		for (int m = 0; m < ps.n_outer; m++) c ^= ps.two[tid][m] & (0u - (uint32_t)((outer >> m) & 1));
-		for (int b = 0; b < P.log_rate; b++) c ^= ps.twc[tid][b] & (0u - (uint32_t)((coset >> b) & 1));
-		cu_w[tid] = c;
-	}
+	if (tid < ps.k) cu_w[tid] = uniform_tw(ps, tid, ta.outer, ta.coset, P.log_rate);
 	// ---- tile into LDS copy 0: 4096 pieces of 16 bytes, 8 per thread, all loads in flight at once
 	constexpr int kRounds = (kTileBlocks * 8 * L + kSplitNT - 1) / kSplitNT;
 	uint4 g[kRounds];
@@ -535,24 +457,17 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 	for (int r = 0; r < kRounds; r++) {
 		const int u = tid + r * kSplitNT;
 		if (IN_COMPACT) {
-			const int q = u / (8 * L), j = u % (8 * L);
-			g[r] = ld_stream(src + (ooff | tile_off(q)) * L + 4 * j);
+			g[r] = ld_stream(src + compact_off<L>(ps, ooff, u));
 		} else {
 			const int pl = u >> 10, rr = u & 1023, q = rr >> 3, j = rr & 7;  // plane, block, 16-B chunk
-			g[r] = ld_stream(src + (ooff | tile_off(q)) * L + 32 * pl + 4 * j);
+			g[r] = ld_stream(src + bitsliced_off<L>(ps, ooff, q, pl, j));
 		}
 	}
 #pragma unroll
 	for (int r = 0; r < kRounds; r++) {
 		const int u = tid + r * kSplitNT;
 		if (IN_COMPACT) {
-			const int q = u / (8 * L), j = u % (8 * L);
-			const uint32_t wd[4] = {g[r].x, g[r].y, g[r].z, g[r].w};
-#pragma unroll
-			for (int c = 0; c < 4; c++) {
-				const int word = 4 * j + c;
-				lds[(word % L) * kPlane + q * kLimbStride + word / L] = wd[c];
-			}
+			compact_to_planes<L>(lds, u, g[r]);
 		} else {
 			const int pl = u >> 10, rr = u & 1023, q = rr >> 3, j = rr & 7;
 			*(uint4*)(lds + pl * kPlane + q * kLimbStride + 4 * j) = g[r];
@@ -561,13 +476,7 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 	__syncthreads();
 	if (IN_COMPACT) {
 		// 512 per-(block, limb) 32x32 transposes, one per thread
-		uint32_t* x = lds + (tid >> 7) * kPlane + (tid & 127) * kLimbStride;
-		uint32_t r[32];
-#pragma unroll
-		for (int i = 0; i < 32; i += 4) *(uint4*)(r + i) = *(const uint4*)(x + i);
-		transpose32(r);
-#pragma unroll
-		for (int i = 0; i < 32; i += 4) *(uint4*)(x + i) = *(const uint4*)(r + i);
+		transpose_block(lds + (tid >> 7) * kPlane + (tid & 127) * kLimbStride);
 		__syncthreads();
 	}
 	// the stages, instantiated per product half H (its words o = 16 H index register arrays, so they
@@ -610,13 +519,6 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 #pragma unroll
 		for (int i = 0; i < 16; i++) p[i] ^= z[i];
 	};
-	auto tile_tw = [&](int j, int q) -> uint32_t {
-		uint32_t tw = 0;
-#pragma unroll
-		for (int m = 0; m < kBlkBits; m++) tw ^= ps.twt[j][m] & (uint32_t)__builtin_amdgcn_sbfe(q, m, 1);
-		return tw;
-	};
-
 	// ---- tile-bit stages: lane = block pair of limb l, as antt_bs_pass
 	for (int j = ps.k - 1; j >= 0; j--) {
 		const int m = ps.stage_m[j];
@@ -629,7 +531,7 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 		uint32_t V[32], W0[16], W1[16], pr[16];
 #pragma unroll
 		for (int i = 0; i < 32; i += 4) *(uint4*)(V + i) = *(const uint4*)(sv + i);
-		const uint32_t wt = cu_w[j] ^ tile_tw(j, qu);
+		const uint32_t wt = cu_w[j] ^ tile_tw(ps, j, qu);
 #pragma unroll
 		for (int i = 0; i < 16; i++) {
 			W0[i] = (uint32_t)__builtin_amdgcn_sbfe(wt, i, 1);
@@ -657,7 +559,7 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 	for (int u = tid; u < kTileBlocks * 8 * L; u += kSplitNT) {
 		const int pl = u >> 10, r = u & 1023, q = r >> 3, j = r & 7;
 		const uint4 g = *(const uint4*)(fin + pl * kPlane + q * kLimbStride + 4 * j);
-		if (!(BS_DBG(P) & 2)) st_stream(dst + (ooff | tile_off(q)) * L + 32 * pl + 4 * j, g);
+		if (!(BS_DBG(P) & 2)) st_stream(dst + bitsliced_off<L>(ps, ooff, q, pl, j), g);
 	}
 	mark(3);
 	if (TR && lane == 0) {
@@ -769,12 +671,9 @@ static std::vector<BsPass> plan_passes(const bn_antt_plan* plan) {
 // kernel instance per (limbs, role, largest stage field)
 template <int L, int FMAX>
 static const void* kernel_for_f(int role) {
-	switch (role) {
-		case ROLE_FIRST: return (const void*)antt_bs_pass<L, ROLE_FIRST, FMAX>;
-		case ROLE_MID: return (const void*)antt_bs_pass<L, ROLE_MID, FMAX>;
-		case ROLE_LAST: return (const void*)antt_bs_pass<L, ROLE_LAST, FMAX>;
-		default: return (const void*)antt_bs_pass<L, ROLE_SINGLE, FMAX>;
-	}
+	static const void* const by_role[4] = {(const void*)antt_bs_pass<L, ROLE_FIRST, FMAX>, (const void*)antt_bs_pass<L, ROLE_MID, FMAX>,
+	                                       (const void*)antt_bs_pass<L, ROLE_LAST, FMAX>, (const void*)antt_bs_pass<L, ROLE_SINGLE, FMAX>};
+	return by_role[role];
 }
 static const void* kernel_for(int L, int role, int fmax) {
 	if (L == 4) return fmax <= 8 ? kernel_for_f<4, 8>(role) : kernel_for_f<4, 32>(role);
@@ -799,9 +698,6 @@ int pass_fmax(const BsPass& p) {
 	return f;
 }
 
-// tile + one word per stage and wave for the workgroup-uniform twiddle parts
-static size_t lds_bytes(int L) { return ((size_t)L * kPlane + (size_t)L * kMaxStages) * sizeof(uint32_t); }
-
 bool bs_supports(const bn_antt_plan* plan) {
 	return plan->log_h >= kMinLogH && plan->log_h - 5 - kBlkBits <= kMaxOuter && plan->log_rate <= kMaxRateBits;
 }
@@ -810,7 +706,7 @@ int bs_prepare(bn_antt_plan* plan) {
 	for (int L : {1, 4})
 		for (int role = 0; role < 4; role++)
 			for (int f : {8, 32})
-				BN_HIP(hipFuncSetAttribute(kernel_for(L, role, f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(L)));
+				BN_HIP(hipFuncSetAttribute(kernel_for(L, role, f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds_bytes(L)));
 	for (int role : {ROLE_FIRST, ROLE_MID})
 		BN_HIP(hipFuncSetAttribute(split_kernel_for(role), hipFuncAttributeMaxDynamicSharedMemorySize, (int)split_lds_bytes()));
 	// the pass tables are built here, once per plan, so that a bottom pass whose tile is not the
@@ -936,7 +832,7 @@ static BsSel select_pass(bn_antt_plan* plan, const BsPass& pass, size_t ntiles, 
 		return {rr_pass_kernel(plan, pass, ntiles), true, 0, 0};
 	if (plan->variant != 1 && plan->variant != 5) return {nullptr, false, 0, 0};
 	if (use_split(plan, pass, ntiles, kn)) return {split_kernel_for(pass.role), false, kSplitNT, split_lds_bytes()};
-	return {kernel_for(L, pass.role, fmax), false, 64u * (unsigned)L, lds_bytes(L)};
+	return {kernel_for(L, pass.role, fmax), false, 64u * (unsigned)L, tile_lds_bytes(L)};
 }
 
 // BN_TRACE: the phase cycles the waves of one launch left in d_trace (8 words per wave, the slots of

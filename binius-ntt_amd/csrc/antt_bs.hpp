@@ -55,6 +55,15 @@ struct RtPass {
 	uint32_t pat[5][32];  // in-word stage s: bit-lane part of the twiddle words (R0/R1 difference folded)
 };
 
+// Bitsliced fast path (antt_bs.hip, antt_rr.hip), used when bs_supports(plan); bs_prepare sets the
+// plan up for it on creation and on the first change from variant 0.
+bool bs_supports(const bn_antt_plan* plan);
+int bs_prepare(bn_antt_plan* plan);
+int launch_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st);
+int bs_time_passes(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, int reps, hipStream_t st,
+                   float* ms, int max_passes, int* n_out);
+// its inverse (antt_inv.hip): one coset block of evaluations back to coefficients
+int launch_inv_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, int coset, size_t batch, hipStream_t st);
 // pass tables of a plan (built once, cached in the plan)
 const BsPass* bs_passes(bn_antt_plan* plan, size_t* n_passes);
 int pass_fmax(const BsPass& p);

@@ -60,15 +60,12 @@ struct RrParams {
 constexpr int kSlot = 36;                 // LDS words per staged block (32 + 4 pad: conflict-free b128 writes)
 constexpr int kStagePlane = 64 * kSlot;   // one limb plane of a half tile
 
+// ld_stream / st_stream on four consecutive registers
 __device__ __forceinline__ void ld4(const uint32_t* p, uint32_t* r) {
-	const u32x4 v = __builtin_nontemporal_load((const u32x4*)p);
+	const uint4 v = ld_stream(p);
 	r[0] = v.x, r[1] = v.y, r[2] = v.z, r[3] = v.w;
 }
-__device__ __forceinline__ void st4(uint32_t* p, const uint32_t* r) {
-	u32x4 v;
-	v.x = r[0], v.y = r[1], v.z = r[2], v.w = r[3];
-	__builtin_nontemporal_store(v, (u32x4*)p);
-}
+__device__ __forceinline__ void st4(uint32_t* p, const uint32_t* r) { st_stream(p, make_uint4(r[0], r[1], r[2], r[3])); }
 
 __device__ __forceinline__ uint32_t sel(uint32_t m, uint32_t a, uint32_t b) {  // m ? a : b, bitwise
 	return __builtin_amdgcn_bitop3_b32(m, a, b, 0xCA);
@@ -125,15 +122,14 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 	const size_t n = (size_t)1 << P.log_h;
 
 	// tile -> (outer bits, coset, batch)
-	const size_t t = blockIdx.x;
-	const size_t outer = t & (((size_t)1 << ps.n_outer) - 1);
-	const size_t rest = t >> ps.n_outer;
-	const int coset = (int)(rest & ((1u << P.log_rate) - 1));
-	const size_t batch = rest >> P.log_rate;
-	size_t ooff = 0;
-	for (int m = 0; m < ps.n_outer; m++) ooff |= ((outer >> m) & 1) << ps.ob[m];
-	uint32_t* dst = P.dst + (((batch << P.log_rate) + (size_t)coset) * n) * L;
-	const uint32_t* src = IN_COMPACT ? (P.src + batch * n * L) : dst;
+	const TileAddr ta = tile_addr(ps, P.log_rate);
+	const size_t ooff = ta.outer_off;
+	uint32_t* dst = P.dst + (((ta.batch << P.log_rate) + (size_t)ta.coset) * n) * L;
+	const uint32_t* src = IN_COMPACT ? (P.src + ta.batch * n * L) : dst;
+	// tile_off and uniform_tw of antt_bs_dev.hpp, written out: the GF(2^32)-element (L = 1) bottom-pass
+	// instances under the three-waves bound spill, and through the shared helpers (same arithmetic)
+	// their spill counts move (FMAX 16 / 32: 46 -> 24 and 130 -> 18 at ROLE_LAST, 60 -> 17 and
+	// 123 -> 125 at ROLE_SINGLE)
 	auto tile_off = [&](int q) -> size_t {
 		size_t off = 0;
 #pragma unroll
@@ -144,9 +140,9 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 	uint32_t cuv = 0;
 	if (lane < ps.k) {
 		for (int m = 0; m < ps.n_outer; m++)
-			if ((outer >> m) & 1) cuv ^= ps.two[lane][m];
+			if ((ta.outer >> m) & 1) cuv ^= ps.two[lane][m];
 		for (int b = 0; b < P.log_rate; b++)
-			if ((coset >> b) & 1) cuv ^= ps.twc[lane][b];
+			if ((ta.coset >> b) & 1) cuv ^= ps.twc[lane][b];
 	}
 	auto ucu = [&](int j) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)cuv, j); };
 
@@ -338,12 +334,9 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 
 template <int L, int FMAX>
 static const void* kernel_f(int role) {
-	switch (role) {
-		case ROLE_FIRST: return (const void*)antt_rr_pass<L, ROLE_FIRST, FMAX>;
-		case ROLE_MID: return (const void*)antt_rr_pass<L, ROLE_MID, FMAX>;
-		case ROLE_LAST: return (const void*)antt_rr_pass<L, ROLE_LAST, FMAX>;
-		default: return (const void*)antt_rr_pass<L, ROLE_SINGLE, FMAX>;
-	}
+	static const void* const by_role[4] = {(const void*)antt_rr_pass<L, ROLE_FIRST, FMAX>, (const void*)antt_rr_pass<L, ROLE_MID, FMAX>,
+	                                       (const void*)antt_rr_pass<L, ROLE_LAST, FMAX>, (const void*)antt_rr_pass<L, ROLE_SINGLE, FMAX>};
+	return by_role[role];
 }
 static const void* kernel_for(int L, int role, int fmax) {
 	if (L == 4) return fmax <= 8 ? kernel_f<4, 8>(role) : fmax <= 16 ? kernel_f<4, 16>(role) : kernel_f<4, 32>(role);

@@ -89,6 +89,23 @@ def test_batched_inverse(log_h, r, coset, batch, dev):
         assert np.array_equal(got[b], xs[b]), b
 
 
+# the compact kernel at GF(2^128) and the bitsliced tiles at GF(2^32) (one limb plane, L = 1): single
+# pass with a coset, and an upper pass with batch bits in the tile index
+@pytest.mark.parametrize("bits,log_h,r,coset,batch", [(128, 8, 1, 1, 3), (32, 12, 1, 1, 3), (32, 13, 0, 0, 2)])
+def test_batched_inverse_compact_and_gf32(bits, log_h, r, coset, batch, dev):
+    n, limbs = 1 << log_h, bits // 32
+    ntt = _ntt(log_h, r, bits)
+    if bits == 128:
+        xs = np.stack([O.fill128(0xBA7C4 + 16 * log_h + b, 0x5EED0000 + b, n) for b in range(batch)])
+    else:
+        xs = np.stack([O.mt_fill(0xBA7C4 + 16 * log_h + b, n) for b in range(batch)])
+    Y = _forward(ntt, xs, dev, batch=batch).reshape(batch, n << r, limbs)
+    ys = np.ascontiguousarray(Y[:, coset * n:(coset + 1) * n])
+    got = _inverse(ntt, ys, dev, coset, batch=batch).reshape(batch, n, limbs)
+    for b in range(batch):
+        assert np.array_equal(got[b], xs[b].reshape(n, limbs)), b
+
+
 @pytest.mark.parametrize("log_h", [13, 20])
 def test_variants_agree(log_h, dev):
     # variant 0 at 13 runs the multi-group compact inverse; 1, 4 and 5 the bitsliced LDS tiles

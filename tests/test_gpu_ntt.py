@@ -75,6 +75,25 @@ def test_gf128_batched(dev):
     assert np.array_equal(y, O.antt128_batch(xs, log_h, 0))
 
 
+@pytest.mark.parametrize("bits,log_h,r,batch", [(128, 8, 1, 3), (128, 11, 0, 2), (32, 10, 2, 3)])
+def test_compact_kernel_batched(bits, log_h, r, batch, dev):
+    # log_h < 12: the compact kernel, one transform of the batch after the other, each with its own
+    # input and its own 2^r coset blocks of the output
+    n = 1 << log_h
+    if bits == 128:
+        xs = np.stack([O.fill128(0xC0B0 + 16 * log_h + b, 0x5EED0000 + b, n) for b in range(batch)])
+        ntt = B.AdditiveNTT(B.AdditiveNTTConf(log_h, r, B.FanPaarTowerField(7)))
+        y = _run_device(ntt, xs.reshape(-1), dev, batch=batch).reshape(batch, n << r, 4)
+        for b in range(batch):
+            assert np.array_equal(y[b], O.antt128(xs[b], log_h, r)), b
+    else:
+        xs = np.stack([O.mt_fill(0xC0B0 + 16 * log_h + b, n) for b in range(batch)])
+        ntt = B.AdditiveNTT(B.AdditiveNTTConf(log_h, r, B.FanPaarTowerField(5)))
+        y = _run_device(ntt, xs.reshape(-1), dev, batch=batch).reshape(batch, n << r)
+        for b in range(batch):
+            assert np.array_equal(y[b], O.antt32(xs[b], log_h, r)), b
+
+
 @pytest.mark.parametrize("log_h,r,batch", [(20, 2, 2), (21, 1, 1), (19, 3, 3)])
 def test_gf128_cosets_at_full_launches(log_h, r, batch, dev):
     # coset bits on launches of many tiles per CU (the LDS-tile passes with their coset twiddle
