@@ -910,6 +910,17 @@ int launch_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t 
 // lane bits that lane coordinate c_k depends on
 static const int kCoordDeps[6][2] = {{0, 2}, {1, 2}, {2, -1}, {3, -1}, {4, -1}, {5, -1}};
 
+// Sub-field class of stage j of a pass for the register-tile block stages: the smallest of 0 (every
+// twiddle of the stage is zero), 2, 4 bits that holds every contribution of the stage (tile, outer
+// and coset bits: a twiddle is an XOR of them), else the pass's own 8 / 16 / 32 (BsPass::field)
+static int rt_stage_class(const BsPass& p, int j) {
+	uint32_t acc = 0;
+	for (int m = 0; m < kBlkBits; m++) acc |= p.twt[j][m];
+	for (int m = 0; m < kMaxOuter; m++) acc |= p.two[j][m];
+	for (int c = 0; c < kMaxRateBits; c++) acc |= p.twc[j][c];
+	return acc == 0 ? 0 : acc < 4u ? 2 : acc < 16u ? 4 : p.field[j];
+}
+
 int make_rt(const BsPass& p, bool bottom, RtPass* out) {
 	RtPass r;
 	memset(&r, 0, sizeof r);
@@ -925,7 +936,7 @@ int make_rt(const BsPass& p, bool bottom, RtPass* out) {
 	for (int j = 0; j < p.k; j++)
 		if (p.stage_m[j] >= 0) {
 			r.jm[p.stage_m[j]] = j;
-			r.field_m[p.stage_m[j]] = p.field[j];
+			r.field_m[p.stage_m[j]] = rt_stage_class(p, j);
 		}
 	r.mlow = kBlkBits;
 	for (int m = 0; m < kBlkBits; m++)
@@ -994,3 +1005,22 @@ int bs_time_passes(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, si
 }
 
 }  // namespace bn
+
+// Host only (no plan, no device): the sub-field class the register-tile table carries for every
+// stage of the upper passes, out[s - 12] for stage s = 12 .. log_h - 1.
+extern "C" int bn_antt_stage_classes(int log_h, int log_rate, int32_t* out, size_t n) {
+	using namespace bn;
+	BN_CHECK_ARG(out != nullptr, "output pointer is NULL");
+	BN_CHECK_ARG(log_rate >= 0 && log_rate <= 4 && log_h + log_rate <= 32, "log_h + log_rate must be <= 32, log_rate in [0,4]");
+	bn_antt_plan plan;
+	plan.log_h = log_h;
+	plan.log_rate = log_rate;
+	plan.width = log_h + log_rate - 1;
+	if (!bs_supports(&plan)) BN_FAIL(BN_ERR_UNSUPPORTED, "the bitsliced passes need log_h >= %d", kMinLogH);
+	BN_CHECK_ARG(n >= (size_t)(log_h - kMinLogH), "output holds %zu entries, need %d", n, log_h - kMinLogH);
+	subspace_evals(log_h, log_rate, plan.s_host);
+	const std::vector<BsPass> passes = plan_passes(&plan);
+	for (size_t i = 0; i + 1 < passes.size(); i++)
+		for (int j = 0; j < passes[i].k; j++) out[passes[i].lo + j - kMinLogH] = rt_stage_class(passes[i], j);
+	return BN_OK;
+}

@@ -45,7 +45,7 @@ struct RtPass {
 	int bb[kBlkBits];
 	int ob[kMaxOuter];
 	int jm[kBlkBits];       // stage index (s - lo) of the block stage on tile bit m, -1 if none
-	int field_m[kBlkBits];  // its twiddle sub-field
+	int field_m[kBlkBits];  // its class: 0 (every twiddle zero), 2, 4 or the pass table's 8 / 16 / 32
 	int field_s[5];         // in-word stages s = 0..4 (bottom pass)
 	uint32_t tau[kBlkBits][6];  // block stage on tile bit m: twiddle contribution of lane bit b
 	uint32_t tau_iw[5][6];      // in-word stage s: lane-bit contributions to block R1's twiddle

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "antt_bs.hpp"
@@ -116,6 +117,9 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 	constexpr bool IN_COMPACT = ROLE == ROLE_FIRST || ROLE == ROLE_SINGLE;
 	constexpr bool LAST = ROLE == ROLE_LAST || ROLE == ROLE_SINGLE;
 	constexpr int NT = 64 * L;
+	// the upper passes whose twiddles all lie in GF(2^8) run each block stage with the circuit of its
+	// class 0 / 2 / 4 / 8; the bottom pass and the FMAX 16 / 32 instances round the small classes up to 8
+	constexpr bool SMALL = FMAX <= 8 && !LAST;
 	const RtPass& ps = P.p;
 	const int tid = threadIdx.x;
 	const int w = tid >> 6, lane = tid & 63;
@@ -219,17 +223,54 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 
 	// ---- block stages on tile bits 6 .. mlow (the bottom pass runs all seven)
 	const int mlow = LAST ? 0 : ps.mlow;
+	if constexpr (SMALL) {
+		// one block stage with the circuit of class C (RtPass::field_m): 8 = bsm3x4_fma_tw, 4 / 2 = every
+		// twiddle of the stage lies in GF(2^4) / GF(2^2), the product on the limb's 8 nibbles / 16 bit
+		// pairs, 0 = every twiddle is zero: no twiddle and no product, u stays as it is
+		auto stage = [&](int m, auto cc) {
+			constexpr int C = decltype(cc)::value;
+			if (m < kBlkBits - 1) xchg(R0, R1, lane, m);
+			if (C != 0) {
+				uint32_t tw = ucu(ps.jm[m]);
+#pragma unroll
+				for (int b = 0; b < 6; b++) tw ^= ps.tau[m][b] & bitmask(lane, b);
+				__builtin_amdgcn_sched_barrier(0);
+				if (C == 2) bsm1x16_fma_tw(R1, tw, R0);  // u ^= w * v
+				else if (C == 4) bsm2x8_fma_tw(R1, tw, R0);
+				else bsm3x4_fma_tw(R1, tw, R0);
+				__builtin_amdgcn_sched_barrier(0);
+			}
+#pragma unroll
+			for (int i = 0; i < 32; i++) R1[i] ^= R0[i];  // v ^= u
+		};
+		// One loop per class, in the order the classes come at log_rate 0 (0, 2, 4, 8 from the top
+		// stage down), and not one loop that selects the circuit per stage: two circuits behind a
+		// branch in one loop body make the register allocator copy R0/R1 at their merge (first pass
+		// at L = 4: 136 VGPRs, 147 with the class-0 skip, against 122 this way; four waves need 128).
+		// A stage whose class is below its loop's gets a correct, merely larger, circuit, so any
+		// order of classes stays exact.
+		int m = kBlkBits - 1;
 #pragma unroll 1
-	for (int m = kBlkBits - 1; m >= mlow; m--) {
-		if (m < kBlkBits - 1) xchg(R0, R1, lane, m);
-		uint32_t tw = ucu(ps.jm[m]);
+		for (; m >= mlow && ps.field_m[m] == 0; m--) stage(m, std::integral_constant<int, 0>());
+#pragma unroll 1
+		for (; m >= mlow && ps.field_m[m] <= 2; m--) stage(m, std::integral_constant<int, 2>());
+#pragma unroll 1
+		for (; m >= mlow && ps.field_m[m] <= 4; m--) stage(m, std::integral_constant<int, 4>());
+#pragma unroll 1
+		for (; m >= mlow; m--) stage(m, std::integral_constant<int, 8>());
+	} else {
+#pragma unroll 1
+		for (int m = kBlkBits - 1; m >= mlow; m--) {
+			if (m < kBlkBits - 1) xchg(R0, R1, lane, m);
+			uint32_t tw = ucu(ps.jm[m]);
 #pragma unroll
-		for (int b = 0; b < 6; b++) tw ^= ps.tau[m][b] & bitmask(lane, b);
-		__builtin_amdgcn_sched_barrier(0);
-		fma_tw<FMAX>(ps.field_m[m], tw, R1, R0);  // u ^= w * v
-		__builtin_amdgcn_sched_barrier(0);
+			for (int b = 0; b < 6; b++) tw ^= ps.tau[m][b] & bitmask(lane, b);
+			__builtin_amdgcn_sched_barrier(0);
+			fma_tw<FMAX>(ps.field_m[m], tw, R1, R0);  // u ^= w * v (classes 0 / 2 / 4 rounded up to 8)
+			__builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-		for (int i = 0; i < 32; i++) R1[i] ^= R0[i];  // v ^= u
+			for (int i = 0; i < 32; i++) R1[i] ^= R0[i];  // v ^= u
+		}
 	}
 
 	if (LAST) {

@@ -71,6 +71,7 @@ def lib():
         "bn_antt_time_passes": (i32, [vp, vp, vp, sz, i32, vp, ctypes.POINTER(ctypes.c_float), i32, ctypes.POINTER(i32)]),
         "bn_antt_pass_kernel_name": (i32, [vp, i32, ctypes.c_char_p, sz]),
         "bn_antt_inword_tables": (i32, [i32, i32, u32p, sz]),
+        "bn_antt_stage_classes": (i32, [i32, i32, ctypes.POINTER(ctypes.c_int32), sz]),
         "bn_gf128_mul_device": (i32, [vp, vp, vp, sz, vp]),
         "bn_gf128_mul_bitsliced_device": (i32, [vp, vp, vp, sz, vp]),
         "bn_gf32_mul_device": (i32, [vp, vp, vp, sz, vp]),

@@ -983,8 +983,10 @@ def main(argv=None):
 def write_ntt_header(path):
     """The second header: the two GF(2^32) circuits of the NTT passes (mul_tw and the scalar top
     stage), built flat and emitted by PackedEmitter. They are variants of bsm5_mul and bsm5_mul_w,
-    which keep their form in the first header for their other consumers. Their instruction counts
-    go to stderr as `ntt <name> <count>`."""
+    which keep their form in the first header for their other consumers; and the GF(2^4) / GF(2^2)
+    forms of bsm3x4_fma_tw (bsm2x8_fma_tw, bsm1x16_fma_tw, same emitter and barrier spacing) for
+    the register-tile passes' small-sub-field stages. Their instruction counts go to stderr as
+    `ntt <name> <count>`."""
     parts = ["// GENERATED by binius-ntt_amd/tools/gen_bitsliced.py -- do not edit.",
              "// The additive NTT passes' GF(2^32) multipliers: the Karatsuba tower of bitsliced_gen.hpp with",
              "// the recombination's double additions cancelled and every multi-operand XOR packed by",
@@ -999,6 +1001,16 @@ def write_ntt_header(path):
              "const uint32_t* __restrict__ a, uint32_t w, uint32_t* __restrict__ out", wl)):
         parts.append("/* %s: %s; %d instructions */" % (name, what, count_ops(lines)))
         parts.append("__host__ __device__ __forceinline__ void %s(%s) {\n\t" % (name, sig) + "\n\t".join(lines) + "\n}\n")
+        print("ntt %s %d" % (name, count_ops(lines)), file=sys.stderr)
+    # the register-tile passes' stages whose twiddles all lie in GF(2^4) or GF(2^2) (the top stages
+    # of a transform at log_rate 0): bsm3x4_fma_tw's form one and two tower levels further down
+    for h in (2, 1):
+        cnt = 32 >> h
+        name = "bsm%dx%d_fma_tw" % (h, cnt)
+        lines = gen_fma_tw_multi(h, cnt)
+        parts.append("/* %s: out ^= a * w on the %d GF(2^%d) coordinates of 32-word limbs, w compact (bits 0 .. %d), "
+                     "twiddle leaves shared; out must not alias a; %d instructions */" % (name, cnt, 1 << h, (1 << h) - 1, count_ops(lines)))
+        parts.append(fn("void %s(const uint32_t* __restrict__ a, uint32_t w, uint32_t* __restrict__ out)" % name, lines))
         print("ntt %s %d" % (name, count_ops(lines)), file=sys.stderr)
     parts.append("}  // namespace bn")
     with open(path, "w") as f:

@@ -131,6 +131,14 @@ int bn_antt_pass_kernel_name(bn_antt_plan* plan, int pass, char* buf, size_t cap
  *     field     8/16/32: the sub-field holding every twiddle of the stage
  * BN_ERR_UNSUPPORTED for log_h < 12, BN_ERR_INVALID if out_words is too small. */
 int bn_antt_inword_tables(int log_h, int log_rate, uint32_t* out, size_t out_words);
+/* Test hook (no reference counterpart; host only: no plan, no device): the sub-field class that
+ * the register-tile pass table carries for every stage above the bottom pass of a (log_h, log_rate)
+ * transform, out[s - 12] for stage s = 12 .. log_h - 1: the smallest of 0 (every twiddle of the
+ * stage is zero), 2, 4, 8, 16, 32 bits that holds every twiddle of the stage. The first pass's
+ * GF(2^8) register-tile kernels pick the stage's multiply circuit by it (0: none, 2: bsm1x16_fma_tw,
+ * 4: bsm2x8_fma_tw, 8: bsm3x4_fma_tw); every other kernel rounds 0 / 2 / 4 up to 8.
+ * BN_ERR_UNSUPPORTED for log_h < 12, BN_ERR_INVALID if n < log_h - 12. */
+int bn_antt_stage_classes(int log_h, int log_rate, int32_t* out, size_t n);
 
 /* ------------------------------------------------------------------------------------
  * Binary tower field arithmetic (src/ulvt/finite_fields/)
