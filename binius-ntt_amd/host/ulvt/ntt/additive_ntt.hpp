@@ -59,6 +59,29 @@ public:
 		ulvt::bn_check(bn_antt_inverse_device(plan, d_in, d_out, coset, batch, stream));
 	}
 
+	// FRI-Binius fold (no reference counterpart; GF(2^128) plans): the codeword of round `round`
+	// (round 0: apply()'s output) folded `arity` times with challenges[0 .. 4*arity), challenges[0..3]
+	// first. Returns false, with no other effect, unless input.size == 2^(log_h+log_rate-round),
+	// input.order == IN_ORDER, 1 <= arity <= log_h - round and output holds input.size >> arity
+	// elements; otherwise writes that many elements, sets output.order = IN_ORDER and returns after a
+	// full sync.
+	bool fri_fold(const NTTData<T>& input, NTTData<T>& output, int round, const uint32_t* challenges, int arity) {
+		if (round < 0 || arity < 1 || round + arity > ntt_conf.log_h) return false;
+		if (input.size != ((size_t)1 << (ntt_conf.log_h + ntt_conf.log_rate - round)) || input.order != DataOrder::IN_ORDER)
+			return false;
+		if (output.size < (input.size >> arity)) return false;
+		ulvt::bn_check(bn_antt_fri_fold_host(plan, input.data.get(), input.size, round, arity, challenges, output.data.get()));
+		output.order = DataOrder::IN_ORDER;
+		return true;
+	}
+
+	// `batch` device-resident folds sharing the challenges (host memory, read before the call
+	// returns), one launch, asynchronous on `stream`.
+	void fri_fold_device(const void* d_in, void* d_out, int round, const uint32_t* challenges, int arity, size_t batch = 1,
+	                     void* stream = nullptr) {
+		ulvt::bn_check(bn_antt_fri_fold_device(plan, d_in, d_out, round, arity, challenges, batch, stream));
+	}
+
 	// 0: compact tiles, per-butterfly twiddles (default for log_h < 12); 1: bitsliced LDS tiles;
 	// 4: bitsliced register tiles; 5: 4 for the GF(2^8)-twiddle passes, 1 for the others (default
 	// for log_h >= 12)

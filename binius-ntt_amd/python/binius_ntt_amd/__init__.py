@@ -63,6 +63,8 @@ def lib():
         "bn_antt_forward_device": (i32, [vp, vp, vp, sz, vp]),
         "bn_antt_inverse_device": (i32, [vp, vp, vp, i32, sz, vp]),
         "bn_antt_inverse_host": (i32, [vp, vp, sz, i32, vp]),
+        "bn_antt_fri_fold_device": (i32, [vp, vp, vp, i32, i32, u32p, sz, vp]),
+        "bn_antt_fri_fold_host": (i32, [vp, vp, sz, i32, i32, u32p, vp]),
         "bn_antt_get_subspace_evals": (i32, [vp, u32p, sz]),
         "bn_antt_plan_query": (i32, [vp, i32, ctypes.POINTER(ctypes.c_int64)]),
         "bn_antt_plan_set_variant": (i32, [vp, i32]),
@@ -298,6 +300,46 @@ class AdditiveNTT:
         _check_device_tensor(d_out, n, "d_out")
         _check(lib().bn_antt_inverse_device(self._plan, _ptr(d_in), _ptr(d_out), coset, batch,
                                             _stream(stream, self.conf.device)))
+
+    @staticmethod
+    def _challenges(challenges):
+        ch = np.ascontiguousarray(challenges, dtype=np.uint32)
+        if ch.ndim != 2 or ch.shape[1] != 4:
+            raise ValueError("challenges must be an (arity, 4) uint32 array")
+        return ch, ch.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+
+    def fri_fold(self, inp, out, round, challenges):
+        """FRI-Binius fold of one host codeword at round `round` (bn_antt_fri_fold_host) with the
+        (arity, 4) uint32 `challenges`, challenges[0] first; no reference counterpart. False (no
+        other effect) unless inp.size == 2^(log_h+log_rate-round) and inp.order == IN_ORDER; fills
+        out with inp.size >> arity elements synchronously."""
+        ch, chp = self._challenges(challenges)
+        log_in = self.conf.log_h + self.conf.log_rate - round
+        if round < 0 or log_in < 0 or inp.size != 1 << log_in or inp.order != DataOrder.IN_ORDER:
+            return False
+        src = np.ascontiguousarray(inp.data, dtype=np.uint32)
+        assert src.size == inp.size * self.limbs
+        n_out = inp.size >> len(ch)
+        dst = out.data
+        if dst.size != n_out * self.limbs:
+            dst = np.zeros((n_out,) if self.limbs == 1 else (n_out, self.limbs), np.uint32)
+        _check(lib().bn_antt_fri_fold_host(self._plan, src.ctypes.data, inp.size, round, len(ch), chp, dst.ctypes.data))
+        out.data = dst
+        out.size = n_out
+        out.order = DataOrder.IN_ORDER
+        return True
+
+    def fri_fold_device(self, d_in, d_out, round, challenges, batch=1, stream=None):
+        """Device-resident fold of `batch` codewords of round `round` with the (arity, 4) uint32
+        host array `challenges` (the arity is its length), in one launch; async on `stream`
+        (default: torch's current stream of the plan's device). d_in is left untouched."""
+        ch, chp = self._challenges(challenges)
+        if round >= 0 and len(ch) >= 1 and round + len(ch) <= self.conf.log_h:  # else: the library's own error
+            n = (1 << (self.conf.log_h + self.conf.log_rate - round)) * self.limbs * batch
+            _check_device_tensor(d_in, n, "d_in")
+            _check_device_tensor(d_out, n >> len(ch), "d_out")
+        _check(lib().bn_antt_fri_fold_device(self._plan, _ptr(d_in), _ptr(d_out), round, len(ch), chp, batch,
+                                             _stream(stream, self.conf.device)))
 
     def subspace_evals(self):
         lh, w = self.conf.log_h, self.conf.log_h + self.conf.log_rate - 1

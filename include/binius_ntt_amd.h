@@ -83,6 +83,35 @@ int bn_antt_inverse_device(bn_antt_plan* plan, const void* d_in, void* d_out, in
  * effect otherwise); `out` receives 2^log_h elements. */
 int bn_antt_inverse_host(bn_antt_plan* plan, const void* in, size_t in_elems, int coset, void* out);
 
+/* FRI-Binius codeword folding (Diamond-Posen; no reference counterpart), GF(2^128) plans only
+ * (BN_ERR_UNSUPPORTED for a 32-bit plan: the challenges live in GF(2^128)). Bit-exact.
+ * The codeword at round i is 2^log_rate blocks, coset-major, of m_i = 2^(log_h-i) compact elements;
+ * round 0 is the output of bn_antt_forward_device. One round i with challenge r maps block c from
+ * m_i to m_i/2 elements: for j < m_i/2, with t the transform's own twiddle of stage i, block j,
+ * coset c (the XOR of s[i][k] over the set bits k < log_h+log_rate-1-i of (c << (log_h-1-i)) | j,
+ * a GF(2^32) value that multiplies limb by limb),
+ *   u = in[c][2j], v = in[c][2j+1]
+ *   v' = u ^ v                         (odd part)
+ *   u' = u ^ t*v'                      (even part)
+ *   out[c][j] = u' ^ r*(u' ^ v')       ((1-r) u' + r v', full GF(2^128) product)
+ * A call folds rounds round .. round+arity-1 with challenges r_0 .. r_{arity-1} (r_0 first) in one
+ * launch: the input is read once and the output written once. Folding the codeword of x through all
+ * log_h rounds leaves 2^log_rate equal elements, the multilinear extension of x at r (bit i of the
+ * index pairs with r_i): bn_multilinear_composition_eval(x, log_h, 1, challenges reversed).
+ * `challenges` is host memory, arity x 4 words, read before the call returns (passed to the kernel
+ * by value: no staging copy, the call stays asynchronous on `stream`). `batch` codewords share the
+ * challenges: codeword b reads d_in + b*2^(log_h+log_rate-round) elements and writes
+ * d_out + b*2^(log_h+log_rate-round-arity) elements. d_in is not written.
+ * BN_ERR_INVALID, with nothing launched: a NULL plan, buffer or challenges, round < 0, arity outside
+ * [1, 8], round + arity > log_h, batch == 0, overlapping d_in and d_out ranges. */
+int bn_antt_fri_fold_device(bn_antt_plan* plan, const void* d_in, void* d_out, int round, int arity,
+                            const uint32_t* challenges, size_t batch, void* stream);
+/* The same on one codeword in host memory, synchronous, through the plan's own stream like
+ * bn_antt_inverse_host. in_elems must equal 2^(log_h+log_rate-round) (BN_ERR_INVALID with no other
+ * effect otherwise); `out` receives 2^(log_h+log_rate-round-arity) elements. */
+int bn_antt_fri_fold_host(bn_antt_plan* plan, const void* in, size_t in_elems, int round, int arity,
+                          const uint32_t* challenges, void* out);
+
 /* Copies the plan's normalised subspace-evaluation table s[i][j] (GF(2^32) values,
  * log_h rows x (log_h+log_rate-1) columns, row-major) to host memory. */
 int bn_antt_get_subspace_evals(const bn_antt_plan* plan, uint32_t* out, size_t out_words);

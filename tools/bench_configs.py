@@ -22,6 +22,11 @@ qm  QM31 sumcheck (prime-field sibling), two columns of 2^N Q
 intt (only with --only intt) inverse additive NTT, GF(2^128), r = 0, 2^20 and 2^24: the inverse
     next to the forward under set_variant(1) (the same products and LDS traffic) and the forward
     default, all three in one process, ms per transform.
+fold (only with --only fold) FRI-Binius fold of a 2^24-element GF(2^128) codeword (log_h 22, log_rate
+    2): round 0 at arity 1 and arity 4, rounds 0-3 singly, the full schedule 4+4+4+4+4+2, and
+    bn_gf128_mul_device on 2^23 products (the arity-1 round's traffic and full-product count) in the
+    same process; ms per call, the two ratios DESIGN.md section 5.8 states bounds for, and the
+    fractions of HBM peak.
 Every line is one JSON object.
 """
 import argparse
@@ -134,6 +139,68 @@ def intt_line(dev, out, log_h):
          "ms_forward_default": ms_fwd, "forward_default_variant": default,
          "inverse_over_forward_variant1": ms_inv / ms_fwd1,
          "hbm_gbps_algorithmic": 32.0 * n / (ms_inv * 1e-3) / 1e9})
+
+
+HBM_PEAK = 8.0e12  # bytes/s, MI355X specification
+
+
+def fold_line(dev, out, log_h=22, log_rate=2, reps=30):
+    """FRI-Binius fold of a 2^(log_h+log_rate)-element GF(2^128) codeword: round 0 at arity 1 and 4,
+    rounds 0..3 singly, the full schedule 4+4+...+rest, and bn_gf128_mul_device on half as many
+    products as the codeword has elements (the traffic and full-product count of the arity-1 round)
+    as the yardstick, all in one process; ms per call, device events after a warm-up call."""
+    import torch
+    import binius_ntt_amd as B
+    n = 1 << (log_h + log_rate)
+    g = np.random.default_rng(7)
+    st = torch.cuda.current_stream(dev)
+    ntt = B.AdditiveNTT(B.AdditiveNTTConf(log_h, log_rate, B.FanPaarTowerField(7), device=dev.index or 0))
+    ch = g.integers(0, 2**32, size=(log_h, 4), dtype=np.uint64).astype(np.uint32)
+    bufs = [torch.randint(-2**31, 2**31, (4 * n,), dtype=torch.int32, device=dev),
+            torch.empty(2 * n, dtype=torch.int32, device=dev)]
+
+    def fold(src, dst, rnd, k):
+        ntt.fri_fold_device(src, dst, rnd, ch[rnd:rnd + k], stream=st)
+
+    def run(schedule, rnd=0):
+        src = 0
+        for k in schedule:
+            fold(bufs[src], bufs[1 - src], rnd, k)
+            rnd, src = rnd + k, 1 - src
+
+    def hbm_bytes(schedule, rnd=0):
+        b = 0
+        for k in schedule:
+            b += 16 * (n >> rnd) + 16 * (n >> (rnd + k))
+            rnd += k
+        return b
+
+    # the yardstick first and last: the spread of the same call within the run
+    a, b, o = bufs[0][:2 * n], bufs[0][2 * n:], bufs[1]
+    ms_mul = [ev_time(lambda: B.gf128_mul(a, b, o, stream=st), reps, st)]
+    ms_a1 = ev_time(lambda: run([1]), reps, st)
+    ms_a4 = ev_time(lambda: run([4]), reps, st)
+    # rounds 0..3 singly, each on a state of its own size (the values do not matter to the time)
+    ms_single = [ev_time(lambda r=r: fold(bufs[0], bufs[1], r, 1), reps, st) for r in range(4)]
+    full = [4] * (log_h // 4) + ([log_h % 4] if log_h % 4 else [])
+    ms_full = ev_time(lambda: run(full), reps, st)
+    ms_mul.append(ev_time(lambda: B.gf128_mul(a, b, o, stream=st), reps, st))
+    mul = min(ms_mul)
+
+    def peak(schedule, ms):
+        return hbm_bytes(schedule) / (ms * 1e-3) / HBM_PEAK
+
+    out({"config": "fold", "workload": "FRI-Binius fold of a 2^%d-element GF(2^128) codeword (log_h %d, log_rate %d)"
+         % (log_h + log_rate, log_h, log_rate), "kernel": "bn::antt_fold",
+         "value": n / (ms_full * 1e-3), "unit": "codeword elements/s (full schedule)",
+         "ms_arity1_round0": ms_a1, "ms_arity4_round0": ms_a4, "ms_single_rounds_0_3": ms_single,
+         "ms_full_schedule": ms_full, "full_schedule": full,
+         "ms_gf128_mul_2p%d" % (log_h + log_rate - 1): ms_mul,
+         "arity1_over_gf128_mul": ms_a1 / mul, "bound_arity1_over_gf128_mul": 1.5,
+         "arity4_over_four_single_rounds": ms_a4 / sum(ms_single), "bound_arity4_over_four_single_rounds": 1.0,
+         "hbm_peak_fraction_arity1": peak([1], ms_a1), "hbm_peak_fraction_arity4": peak([4], ms_a4),
+         "hbm_peak_fraction_full_schedule": peak(full, ms_full),
+         "hbm_peak_fraction_gf128_mul": 24.0 * n / (mul * 1e-3) / HBM_PEAK, "hbm_peak_bytes_per_s": HBM_PEAK})
 
 
 def c4(dev, out, nvars, ds):
@@ -342,6 +409,8 @@ def main():
     if "intt" in only:
         intt_line(dev, out, 20)
         intt_line(dev, out, 24)
+    if "fold" in only:
+        fold_line(dev, out)
     if a.out:
         with open(a.out, "w") as f:
             for d in lines:
