@@ -22,28 +22,6 @@
 
 namespace bn {
 
-void subspace_evals(int log_h, int log_rate, std::vector<uint32_t>& s) {
-	const int width = log_h + log_rate - 1;
-	s.assign((size_t)log_h * (size_t)std::max(width, 1), 0u);
-	auto at = [&](int i, int j) -> uint32_t& { return s[(size_t)i * (size_t)width + (size_t)j]; };
-	std::vector<uint32_t> norm((size_t)std::max(log_h, 1));
-	for (int i = 1; i < log_h + log_rate; i++) at(0, i - 1) = 1u << i;
-	norm[0] = 1;
-	for (int i = 1; i < log_h; i++) {
-		const uint64_t np = norm[i - 1];
-		const uint64_t p0 = at(i - 1, 0);
-		norm[i] = (uint32_t)(tw_square(p0, 5) ^ tw_mul(np, p0, 5));
-		for (int j = 1; j < log_h + log_rate - i; j++) {
-			const uint64_t sp = at(i - 1, j);
-			at(i, j - 1) = (uint32_t)(tw_square(sp, 5) ^ tw_mul(np, sp, 5));
-		}
-	}
-	for (int i = 0; i < log_h; i++) {
-		const uint64_t inv = tw_inv(norm[i], 5);
-		for (int j = 0; j < log_h + log_rate - i - 1; j++) at(i, j) = (uint32_t)tw_mul(inv, at(i, j), 5);
-	}
-}
-
 // ------------------------------------------------------------------------------------
 // v0 kernel: one launch per group of up to kTileLog stages. A workgroup owns a tile of
 // 2^(k+c) elements: the k group bits [lo, lo+k) plus the c lowest index bits (so that
@@ -252,39 +230,32 @@ extern "C" int bn_antt_plan_create(int device, int field_bits, int log_h, int lo
 	p->limbs = field_bits / 32;
 	p->width = log_h + log_rate - 1;
 	subspace_evals(log_h, log_rate, p->s_host);
-	int dev_prev = 0;
-	(void)hipGetDevice(&dev_prev);
-	hipError_t e = hipSetDevice(device);
+	DeviceScope ds(device);
+	hipError_t e = ds.err;
 	if (e == hipSuccess) e = hipMalloc(&p->s_dev, std::max<size_t>(p->s_host.size(), 1) * sizeof(uint32_t));
 	if (e == hipSuccess && !p->s_host.empty())
 		e = hipMemcpy(p->s_dev, p->s_host.data(), p->s_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
 	if (e != hipSuccess) {
-		(void)hipSetDevice(dev_prev);
 		bn_antt_plan_destroy(p);
 		BN_FAIL(BN_ERR_HIP, "plan allocation failed: %s", hipGetErrorString(e));
 	}
 	p->variant = 0;
-	if (bs_supports(p)) {
-		int rc = bs_prepare(p);
-		if (rc == BN_OK) dev_variant_override(p);
+	if (bs_supports(log_h, log_rate)) {
+		const int rc = bs_prepare(p);
 		if (rc != BN_OK) {
-			(void)hipSetDevice(dev_prev);
 			bn_antt_plan_destroy(p);
 			return rc;
 		}
+		dev_variant_override(p);
 	}
-	(void)hipSetDevice(dev_prev);
 	*out = p;
 	return BN_OK;
 }
 
 extern "C" int bn_antt_plan_destroy(bn_antt_plan* p) {
 	if (!p) return BN_OK;
-	int dev_prev = 0;
-	(void)hipGetDevice(&dev_prev);
-	(void)hipSetDevice(p->device);
+	DeviceScope ds(p->device);
 	if (p->s_dev) (void)hipFree(p->s_dev);
-	if (p->scratch) (void)hipFree(p->scratch);
 	if (p->h_dev_in) (void)hipFree(p->h_dev_in);
 	if (p->h_dev_out) (void)hipFree(p->h_dev_out);
 	for (const auto& q : p->pending) {
@@ -294,7 +265,6 @@ extern "C" int bn_antt_plan_destroy(bn_antt_plan* p) {
 	}
 	for (auto e : p->ev_pool) (void)hipEventDestroy(e);
 	if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
-	(void)hipSetDevice(dev_prev);
 	delete p;
 	return BN_OK;
 }
@@ -310,50 +280,6 @@ static int forward_device_impl(bn_antt_plan* p, const void* d_in, void* d_out, s
 	return BN_OK;
 }
 
-extern "C" int bn_antt_forward_device(bn_antt_plan* p, const void* d_in, void* d_out, size_t batch, void* stream) {
-	BN_CHECK_ARG(p != nullptr, "plan is NULL");
-	BN_CHECK_ARG(d_in != nullptr && d_out != nullptr, "device buffers must be non-NULL");
-	BN_CHECK_ARG(batch >= 1, "batch must be >= 1");
-	const size_t in_bytes = ((size_t)1 << p->log_h) * p->limbs * 4 * batch;
-	const size_t out_bytes = in_bytes << p->log_rate;
-	const char* a = (const char*)d_in;
-	const char* b = (const char*)d_out;
-	BN_CHECK_ARG(a + in_bytes <= b || b + out_bytes <= a, "d_in and d_out must not overlap");
-	int dev_prev = 0;
-	(void)hipGetDevice(&dev_prev);
-	if (dev_prev != p->device) BN_HIP(hipSetDevice(p->device));
-	int rc = forward_device_impl(p, d_in, d_out, batch, (hipStream_t)stream);
-	if (dev_prev != p->device) (void)hipSetDevice(dev_prev);
-	return rc;
-}
-
-// AdditiveNTT::apply (additive_ntt.cuh:201-265): host in -> host out, synchronous.
-extern "C" int bn_antt_forward_host(bn_antt_plan* p, const void* in, size_t in_elems, void* out) {
-	BN_CHECK_ARG(p != nullptr, "plan is NULL");
-	BN_CHECK_ARG(in != nullptr && out != nullptr, "host buffers must be non-NULL");
-	BN_CHECK_ARG(in_elems == ((size_t)1 << p->log_h), "input has %zu elements, plan expects 2^%d", in_elems, p->log_h);
-	int dev_prev = 0;
-	(void)hipGetDevice(&dev_prev);
-	BN_HIP(hipSetDevice(p->device));
-	const size_t in_bytes = in_elems * p->limbs * 4;
-	const size_t out_bytes = in_bytes << p->log_rate;
-	if (!p->h_dev_in) {
-		BN_HIP(hipMalloc(&p->h_dev_in, in_bytes));
-		BN_HIP(hipMalloc(&p->h_dev_out, out_bytes));
-	}
-	if (!p->own_stream) BN_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
-	BN_HIP(hipMemcpyAsync(p->h_dev_in, in, in_bytes, hipMemcpyHostToDevice, p->own_stream));
-	int rc = forward_device_impl(p, p->h_dev_in, p->h_dev_out, 1, p->own_stream);
-	if (rc != BN_OK) {
-		(void)hipSetDevice(dev_prev);
-		return rc;
-	}
-	BN_HIP(hipMemcpyAsync(out, p->h_dev_out, out_bytes, hipMemcpyDeviceToHost, p->own_stream));
-	BN_HIP(hipStreamSynchronize(p->own_stream));
-	(void)hipSetDevice(dev_prev);
-	return BN_OK;
-}
-
 static int inverse_device_impl(bn_antt_plan* p, const void* d_in, void* d_out, int coset, size_t batch, hipStream_t st) {
 	if (p->variant != 0) return launch_inv_bs(p, (const uint32_t*)d_in, (uint32_t*)d_out, coset, batch, st);
 	const size_t n_words = ((size_t)1 << p->log_h) * p->limbs;
@@ -364,49 +290,61 @@ static int inverse_device_impl(bn_antt_plan* p, const void* d_in, void* d_out, i
 	return BN_OK;
 }
 
-extern "C" int bn_antt_inverse_device(bn_antt_plan* p, const void* d_in, void* d_out, int coset, size_t batch,
-                                      void* stream) {
-	BN_CHECK_ARG(p != nullptr, "plan is NULL");
-	BN_CHECK_ARG(d_in != nullptr && d_out != nullptr, "device buffers must be non-NULL");
-	BN_CHECK_ARG(batch >= 1, "batch must be >= 1");
-	BN_CHECK_ARG(coset >= 0 && coset < (1 << p->log_rate), "coset must be in [0, 2^%d) (got %d)", p->log_rate, coset);
-	const size_t bytes = ((size_t)1 << p->log_h) * p->limbs * 4 * batch;
-	const char* a = (const char*)d_in;
-	const char* b = (const char*)d_out;
-	BN_CHECK_ARG(a + bytes <= b || b + bytes <= a, "d_in and d_out must not overlap");
-	int dev_prev = 0;
-	(void)hipGetDevice(&dev_prev);
-	if (dev_prev != p->device) BN_HIP(hipSetDevice(p->device));
-	int rc = inverse_device_impl(p, d_in, d_out, coset, batch, (hipStream_t)stream);
-	if (dev_prev != p->device) (void)hipSetDevice(dev_prev);
-	return rc;
+// bytes of `batch` blocks of 2^log_h elements
+static size_t block_bytes(const bn_antt_plan* p, size_t batch) { return ((size_t)1 << p->log_h) * p->limbs * 4 * batch; }
+
+extern "C" int bn_antt_forward_device(bn_antt_plan* p, const void* d_in, void* d_out, size_t batch, void* stream) {
+	if (int rc = check_device_args(p, d_in, d_out, batch)) return rc;
+	if (int rc = check_no_overlap(d_in, block_bytes(p, batch), d_out, block_bytes(p, batch) << p->log_rate)) return rc;
+	BN_DEVICE_SCOPE(p->device);
+	return forward_device_impl(p, d_in, d_out, batch, (hipStream_t)stream);
 }
 
-extern "C" int bn_antt_inverse_host(bn_antt_plan* p, const void* in, size_t in_elems, int coset, void* out) {
+extern "C" int bn_antt_inverse_device(bn_antt_plan* p, const void* d_in, void* d_out, int coset, size_t batch,
+                                      void* stream) {
+	if (int rc = check_device_args(p, d_in, d_out, batch)) return rc;
+	BN_CHECK_ARG(coset >= 0 && coset < (1 << p->log_rate), "coset must be in [0, 2^%d) (got %d)", p->log_rate, coset);
+	if (int rc = check_no_overlap(d_in, block_bytes(p, batch), d_out, block_bytes(p, batch))) return rc;
+	BN_DEVICE_SCOPE(p->device);
+	return inverse_device_impl(p, d_in, d_out, coset, batch, (hipStream_t)stream);
+}
+
+static int check_host_args(const bn_antt_plan* p, const void* in, size_t in_elems, const void* out) {
 	BN_CHECK_ARG(p != nullptr, "plan is NULL");
 	BN_CHECK_ARG(in != nullptr && out != nullptr, "host buffers must be non-NULL");
 	BN_CHECK_ARG(in_elems == ((size_t)1 << p->log_h), "input has %zu elements, plan expects 2^%d", in_elems, p->log_h);
-	BN_CHECK_ARG(coset >= 0 && coset < (1 << p->log_rate), "coset must be in [0, 2^%d) (got %d)", p->log_rate, coset);
-	int dev_prev = 0;
-	(void)hipGetDevice(&dev_prev);
-	BN_HIP(hipSetDevice(p->device));
-	const size_t bytes = in_elems * p->limbs * 4;
-	if (!p->h_dev_in) {
-		// the forward staging buffers: the inverse needs 2^log_h elements of each
-		BN_HIP(hipMalloc(&p->h_dev_in, bytes));
-		BN_HIP(hipMalloc(&p->h_dev_out, bytes << p->log_rate));
-	}
-	if (!p->own_stream) BN_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
-	BN_HIP(hipMemcpyAsync(p->h_dev_in, in, bytes, hipMemcpyHostToDevice, p->own_stream));
-	int rc = inverse_device_impl(p, p->h_dev_in, p->h_dev_out, coset, 1, p->own_stream);
-	if (rc != BN_OK) {
-		(void)hipSetDevice(dev_prev);
-		return rc;
-	}
-	BN_HIP(hipMemcpyAsync(out, p->h_dev_out, bytes, hipMemcpyDeviceToHost, p->own_stream));
-	BN_HIP(hipStreamSynchronize(p->own_stream));
-	(void)hipSetDevice(dev_prev);
 	return BN_OK;
+}
+// Host in -> host out, synchronous, one transform: through the plan's staging buffers (allocated on
+// first use: 2^log_h elements in, every coset block out, which holds the inverse's one block too) and
+// its own stream. `launch(d_in, d_out, stream)` runs the transform between the two copies.
+template <class Launch>
+static int host_transform(bn_antt_plan* p, const void* in, void* out, size_t out_bytes, Launch launch) {
+	BN_DEVICE_SCOPE(p->device);
+	const size_t in_bytes = block_bytes(p, 1);
+	if (!p->h_dev_in) BN_HIP(hipMalloc(&p->h_dev_in, in_bytes));
+	if (!p->h_dev_out) BN_HIP(hipMalloc(&p->h_dev_out, in_bytes << p->log_rate));
+	if (!p->own_stream) BN_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
+	BN_HIP(hipMemcpyAsync(p->h_dev_in, in, in_bytes, hipMemcpyHostToDevice, p->own_stream));
+	if (int rc = launch(p->h_dev_in, p->h_dev_out, p->own_stream)) return rc;
+	BN_HIP(hipMemcpyAsync(out, p->h_dev_out, out_bytes, hipMemcpyDeviceToHost, p->own_stream));
+	BN_HIP(hipStreamSynchronize(p->own_stream));
+	return BN_OK;
+}
+
+// AdditiveNTT::apply (additive_ntt.cuh:201-265)
+extern "C" int bn_antt_forward_host(bn_antt_plan* p, const void* in, size_t in_elems, void* out) {
+	if (int rc = check_host_args(p, in, in_elems, out)) return rc;
+	return host_transform(p, in, out, block_bytes(p, 1) << p->log_rate,
+	                      [&](const void* d_in, void* d_out, hipStream_t st) { return forward_device_impl(p, d_in, d_out, 1, st); });
+}
+
+extern "C" int bn_antt_inverse_host(bn_antt_plan* p, const void* in, size_t in_elems, int coset, void* out) {
+	if (int rc = check_host_args(p, in, in_elems, out)) return rc;
+	BN_CHECK_ARG(coset >= 0 && coset < (1 << p->log_rate), "coset must be in [0, 2^%d) (got %d)", p->log_rate, coset);
+	return host_transform(p, in, out, block_bytes(p, 1), [&](const void* d_in, void* d_out, hipStream_t st) {
+		return inverse_device_impl(p, d_in, d_out, coset, 1, st);
+	});
 }
 
 extern "C" int bn_antt_get_subspace_evals(const bn_antt_plan* p, uint32_t* out, size_t out_words) {
@@ -432,14 +370,10 @@ extern "C" int bn_antt_plan_query(const bn_antt_plan* p, int what, int64_t* valu
 extern "C" int bn_antt_plan_set_variant(bn_antt_plan* p, int variant) {
 	BN_CHECK_ARG(p != nullptr, "plan is NULL");
 	BN_CHECK_ARG(valid_variant(variant), "variant must be 0, 1, 4 or 5 (got %d)", variant);
-	if (variant != 0 && !bs_supports(p)) BN_FAIL(BN_ERR_UNSUPPORTED, "variants 1, 4 and 5 need log_h >= 12");
+	if (variant != 0 && !bs_supports(p->log_h, p->log_rate)) BN_FAIL(BN_ERR_UNSUPPORTED, "variants 1, 4 and 5 need log_h >= 12");
 	if (variant != 0 && p->variant == 0) {
-		int prev = 0;
-		(void)hipGetDevice(&prev);
-		BN_HIP(hipSetDevice(p->device));
-		const int rc = bs_prepare(p);
-		(void)hipSetDevice(prev);
-		if (rc != BN_OK) return rc;
+		BN_DEVICE_SCOPE(p->device);
+		if (int rc = bs_prepare(p)) return rc;
 	}
 	p->variant = variant;
 	return BN_OK;
@@ -461,13 +395,9 @@ extern "C" int bn_antt_time_passes(bn_antt_plan* p, const void* d_in, void* d_ou
 	             "NULL argument");
 	BN_CHECK_ARG(batch >= 1 && reps >= 1, "batch and reps must be >= 1");
 	if (p->variant == 0) BN_FAIL(BN_ERR_UNSUPPORTED, "pass timing is built for kernel variants 1, 4 and 5");
-	int dev_prev = 0;
-	(void)hipGetDevice(&dev_prev);
-	if (dev_prev != p->device) BN_HIP(hipSetDevice(p->device));
-	const int rc = bs_time_passes(p, (const uint32_t*)d_in, (uint32_t*)d_out, batch, reps, (hipStream_t)stream,
-	                              ms_per_pass, max_passes, n_passes);
-	if (dev_prev != p->device) (void)hipSetDevice(dev_prev);
-	return rc;
+	BN_DEVICE_SCOPE(p->device);
+	return bs_time_passes(p, (const uint32_t*)d_in, (uint32_t*)d_out, batch, reps, (hipStream_t)stream, ms_per_pass, max_passes,
+	                      n_passes);
 }
 
 extern "C" int bn_antt_pass_kernel_name(bn_antt_plan* p, int pass, char* buf, size_t cap) {

@@ -29,11 +29,14 @@
 // on the way back to LDS moves index bit s-1 out of the bit-lane number for the next stage. The
 // layout is never restored: the host tabulates the twiddle words for the rotated bit-lane meaning
 // (BsPass::pat2), and after stage 0 the transposed pair is written straight to its compact slots.
+//
+// This file: the two kernel families (antt_bs_pass, antt_bs3_pass), the choice of a kernel per pass
+// and launch (select_pass), the launches, and the development build's trace and timing. The pass
+// split and every table are planned on the host in antt_passes.cpp and cached in the plan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
-#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -569,105 +572,8 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 }
 
 // ------------------------------------------------------------------------------------
-// host: pass planning
+// host: kernel selection and launch (the pass tables come from antt_passes.cpp)
 // ------------------------------------------------------------------------------------
-static std::vector<BsPass> plan_passes(const bn_antt_plan* plan) {
-	const int log_h = plan->log_h;
-	const int width = plan->width;
-	auto S = [&](int s, int kk) -> uint32_t {  // s[s][kk], 0 outside the table
-		if (kk < 0 || kk >= width - s) return 0u;
-		return plan->s_host[(size_t)s * width + kk];
-	};
-	std::vector<BsPass> passes;
-	auto make = [&](int lo, int k, bool bottom) {
-		BsPass p{};
-		p.lo = lo;
-		p.k = k;
-		std::vector<int> bits;
-		if (bottom) {
-			for (int b = 5; b < 5 + kBlkBits; b++) bits.push_back(b);
-		} else {
-			// stage bits plus the lowest non-word batch bits (adjacent blocks in memory)
-			for (int b = 5; (int)bits.size() < kBlkBits - k; b++) bits.push_back(b);
-			for (int b = lo; b < lo + k; b++) bits.push_back(b);
-		}
-		for (int m = 0; m < kBlkBits; m++) p.bb[m] = bits[m];
-		p.n_outer = 0;
-		for (int b = 5; b < log_h; b++)
-			if (std::find(bits.begin(), bits.end(), b) == bits.end()) p.ob[p.n_outer++] = b;
-		for (int j = 0; j < k; j++) {
-			const int s = lo + j;
-			// twiddle of a butterfly block = XOR of s[s][kk] over the set bits kk of
-			// (coset << (log_h-1-s)) | (index >> (s+1)); index bit b contributes s[s][b-s-1]
-			uint32_t acc = 0;
-			for (int kk = 0; kk < width - s; kk++) acc |= S(s, kk);
-			p.field[j] = acc < 256u ? 8 : acc < 65536u ? 16 : 32;
-			p.stage_m[j] = -1;
-			for (int m = 0; m < kBlkBits; m++) {
-				if (p.bb[m] == s) p.stage_m[j] = m;
-				p.twt[j][m] = S(s, p.bb[m] - s - 1);
-			}
-			for (int m = 0; m < p.n_outer; m++) p.two[j][m] = S(s, p.ob[m] - s - 1);
-			for (int c = 0; c < plan->log_rate; c++) p.twc[j][c] = S(s, log_h - 1 - s + c);
-			if (s < 5) {
-				// bit-lane p of a word has index bits 0..4 = p: bits s+1..4 contribute per lane
-				for (int i = 0; i < 32; i++) {
-					uint32_t w = 0;
-					for (int b = s + 1; b < 5; b++)
-						if ((S(s, b - s - 1) >> i) & 1) w ^= lane_mask(b);
-					// A's v-lanes sit on the u positions with twiddle cb ^ twt[s][6] (qa, qb differ in
-					// tile bit 6 only): fold that uniform difference in
-					if ((p.twt[j][kBlkBits - 1] >> i) & 1) w ^= ~lane_mask(s);
-					p.pat[s][i] = w;
-				}
-				// packed in-word stages (antt_bs_pass): the stages above s have rotated index bit b
-				// onto bit-lane bit b - 1, and bit-lane bit 4 is the tile's top block bit
-				for (int i = 0; i < 32; i++) {
-					uint32_t w = 0;
-					for (int b = s + 1; b < 5; b++)
-						if ((S(s, b - s - 1) >> i) & 1) w ^= lane_mask(b - 1);
-					if ((p.twt[j][kBlkBits - 1] >> i) & 1) w ^= lane_mask(4);
-					p.pat2[s][i] = w;
-				}
-			}
-		}
-		return p;
-	};
-	// the bottom pass runs all 12 stages of a tile (7 + 6 + 11 at 2^24 measured slower: DESIGN.md
-	// section 5.6)
-	constexpr int bottom_k = kMinLogH;
-	const int rest = log_h - bottom_k;
-	const int n_up = (rest + kBlkBits - 1) / kBlkBits;
-	auto gf8_stage = [&](int s) {
-		uint32_t acc = 0;
-		for (int kk = 0; kk < width - s; kk++) acc |= S(s, kk);
-		return acc < 256u;
-	};
-	// upper passes, executed first (highest stages first)
-	int hi = log_h;
-	for (int i = 0; i < n_up; i++) {
-		const int remaining_up = n_up - i;
-		int k = (hi - bottom_k + remaining_up - 1) / remaining_up;
-		// the first pass takes every top stage whose twiddles lie in GF(2^8) (up to a tile's 7 bits,
-		// as long as the later passes still fit): its register-tile kernel runs near the HBM rate with
-		// VALU to spare, and each stage it takes leaves the GF(2^32) pass one stage less
-		if (i == 0 && remaining_up > 1) {
-			int g = 0;
-			while (g < kBlkBits && hi - g - 1 >= bottom_k && gf8_stage(hi - g - 1)) g++;
-			const int min_first = (hi - bottom_k) - (remaining_up - 1) * kBlkBits;  // the rest must still fit
-			if (g > k && g >= min_first) k = g;
-		}
-		passes.push_back(make(hi - k, k, false));
-		hi -= k;
-	}
-	passes.push_back(make(0, bottom_k, true));
-	for (size_t i = 0; i < passes.size(); i++) {
-		const bool first = i == 0, last = i + 1 == passes.size();
-		passes[i].role = first && last ? ROLE_SINGLE : first ? ROLE_FIRST : last ? ROLE_LAST : ROLE_MID;
-	}
-	return passes;
-}
-
 // kernel instance per (limbs, role, largest stage field)
 template <int L, int FMAX>
 static const void* kernel_for_f(int role) {
@@ -685,23 +591,6 @@ static const void* split_kernel_for(int role) {
 	return role == ROLE_FIRST ? (const void*)antt_bs3_pass<ROLE_FIRST> : (const void*)antt_bs3_pass<ROLE_MID>;
 }
 
-// plan_passes gives the bottom pass the tile bits bb[m] = 5 + m; its kernels rely on it
-static bool bottom_tile_contiguous(const BsPass& p) {
-	for (int m = 0; m < kBlkBits; m++)
-		if (p.bb[m] != 5 + m) return false;
-	return true;
-}
-
-int pass_fmax(const BsPass& p) {
-	int f = 8;
-	for (int j = 0; j < p.k; j++) f = std::max(f, p.field[j]);
-	return f;
-}
-
-bool bs_supports(const bn_antt_plan* plan) {
-	return plan->log_h >= kMinLogH && plan->log_h - 5 - kBlkBits <= kMaxOuter && plan->log_rate <= kMaxRateBits;
-}
-
 int bs_prepare(bn_antt_plan* plan) {
 	for (int L : {1, 4})
 		for (int role = 0; role < 4; role++)
@@ -709,13 +598,12 @@ int bs_prepare(bn_antt_plan* plan) {
 				BN_HIP(hipFuncSetAttribute(kernel_for(L, role, f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds_bytes(L)));
 	for (int role : {ROLE_FIRST, ROLE_MID})
 		BN_HIP(hipFuncSetAttribute(split_kernel_for(role), hipFuncAttributeMaxDynamicSharedMemorySize, (int)split_lds_bytes()));
-	// the pass tables are built here, once per plan, so that a bottom pass whose tile is not the
-	// contiguous run its kernels address fails the plan and never reaches a launch
-	size_t n_passes = 0;
-	const BsPass* passes = bs_passes(plan, &n_passes);
-	if (n_passes == 0 || !bottom_tile_contiguous(passes[n_passes - 1]))
-		BN_FAIL(BN_ERR_UNSUPPORTED, "bottom pass: tile block bits are not index bits 5..11");
-	int rc = rr_prepare(plan);
+	// the pass tables are built here, once per plan, so that a table the kernels cannot run (a bottom
+	// tile that is not one contiguous run, stage bits that are not the top tile bits) fails the plan
+	// and never reaches a launch
+	int rc = plan_pass_tables(plan->log_h, plan->log_rate, plan->s_host, plan->passes, plan->rt);
+	if (rc != BN_OK) return rc;
+	rc = rr_prepare(plan);
 	if (rc != BN_OK) return rc;
 	int cus = 0;
 	BN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, plan->device));
@@ -723,60 +611,6 @@ int bs_prepare(bn_antt_plan* plan) {
 	plan->variant = 5;  // mixed: register tiles for GF(2^8)-only passes, LDS tiles for the others
 	return BN_OK;
 }
-
-const BsPass* bs_passes(bn_antt_plan* plan, size_t* n_passes) {
-	// the pass tables depend only on the plan: built once and cached in it
-	if (plan->bs_passes.empty()) {
-		const auto ps = plan_passes(plan);
-		plan->bs_passes.resize(ps.size() * sizeof(BsPass));
-		memcpy(plan->bs_passes.data(), ps.data(), plan->bs_passes.size());
-	}
-	*n_passes = plan->bs_passes.size() / sizeof(BsPass);
-	return (const BsPass*)plan->bs_passes.data();
-}
-
-}  // namespace bn
-
-// Host only (no plan, no device): the bottom pass's in-word twiddle tables, for checking them
-// against an independent twiddle computation. Layout: see include/binius_ntt_amd.h.
-extern "C" int bn_antt_inword_tables(int log_h, int log_rate, uint32_t* out, size_t out_words) {
-	using namespace bn;
-	constexpr size_t kStageWords = 32 + kBlkBits + kMaxOuter + kMaxRateBits + 1;
-	constexpr size_t kWords = 4 + 1 + kMaxOuter + 5 * kStageWords;
-	BN_CHECK_ARG(out != nullptr, "output pointer is NULL");
-	BN_CHECK_ARG(log_rate >= 0 && log_rate <= 4 && log_h + log_rate <= 32, "log_h + log_rate must be <= 32, log_rate in [0,4]");
-	BN_CHECK_ARG(out_words >= kWords, "output holds %zu words, need %zu", out_words, kWords);
-	bn_antt_plan plan;
-	plan.log_h = log_h;
-	plan.log_rate = log_rate;
-	plan.width = log_h + log_rate - 1;
-	if (!bs_supports(&plan)) BN_FAIL(BN_ERR_UNSUPPORTED, "the bitsliced passes need log_h >= %d", kMinLogH);
-	subspace_evals(log_h, log_rate, plan.s_host);
-	const BsPass p = plan_passes(&plan).back();
-	if (!bottom_tile_contiguous(p)) BN_FAIL(BN_ERR_UNSUPPORTED, "bottom pass: tile block bits are not index bits 5..11");
-	uint32_t* o = out;
-	*o++ = (uint32_t)kWords;
-	*o++ = (uint32_t)kBlkBits;
-	*o++ = (uint32_t)kMaxOuter;
-	*o++ = (uint32_t)kMaxRateBits;
-	*o++ = (uint32_t)p.n_outer;
-	for (int m = 0; m < kMaxOuter; m++) *o++ = (uint32_t)p.ob[m];
-	for (int s = 0; s < 5; s++) {
-		for (int i = 0; i < 32; i++) *o++ = p.pat2[s][i];
-		for (int m = 0; m < kBlkBits; m++) *o++ = p.twt[s][m];
-		for (int m = 0; m < kMaxOuter; m++) *o++ = p.two[s][m];
-		for (int c = 0; c < kMaxRateBits; c++) *o++ = p.twc[s][c];
-		*o++ = (uint32_t)p.field[s];
-	}
-	return BN_OK;
-}
-
-namespace bn {
-
-struct BsDevKnobs {
-	int dbg = 0, split = -1, rr_last = -1;
-	bool trace = false;
-};
 
 // The environment switches of the development build (make BN_DEV=1), all of them. The product
 // build reads none. They measure or select among kernels the product itself launches:
@@ -797,7 +631,7 @@ static BsDevKnobs dev_knobs() {
 	return k;
 }
 
-// GF(2^16/32) LDS-tile upper passes of fewer tiles than two per CU (one 2^20 transform) run
+// GF(2^16/32) LDS-tile upper passes of a small launch (one 2^20 transform) run
 // lane-split (antt_bs3_pass: two waves per product, two waves per SIMD instead of one). 2^20 A/B
 // (EXPERIMENTS.md section 5.1, round 4): upper GF(2^32) pass 0.0139 vs 0.0158 ms, bottom pass 0.0514 vs 0.0496 ms,
 // so the bottom pass keeps one wave per limb and has no lane-split kernel
@@ -805,15 +639,15 @@ static bool use_split(const bn_antt_plan* plan, const BsPass& pass, size_t ntile
 	if (plan->limbs != 4 || pass_fmax(pass) <= 8) return false;
 	if (pass.role == ROLE_LAST || pass.role == ROLE_SINGLE) return false;
 	if (kn.split >= 0) return kn.split != 0;
-	return ntiles < (size_t)2 * (size_t)plan->num_cus;
+	return small_launch(plan, ntiles);
 }
 
-// Bottom pass of a small launch (fewer tiles than two per CU: one wave per SIMD either way) on
+// Bottom pass of a small launch (one wave per SIMD either way) on
 // register tiles, compiled without the three-waves bound (antt_rr.hip rr_pass_kernel): C3 (one 2^20
 // transform) 0.0800-0.0802 vs 0.0822-0.0824 ms on LDS tiles (round 5, EXPERIMENTS.md section 5.1).
 static bool use_rr_last(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
 	if (kn.rr_last == 0 || plan->variant != 5 || plan->limbs != 4 || pass.role != ROLE_LAST) return false;
-	return ntiles < (size_t)2 * (size_t)plan->num_cus;
+	return small_launch(plan, ntiles);
 }
 
 // What runs a pass of `ntiles` tiles (one workgroup per tile). The only place that decides it:
@@ -824,7 +658,7 @@ struct BsSel {
 	unsigned threads;    // otherwise: workgroup size and dynamic LDS of a BsParams kernel of this file
 	size_t lds;
 };
-static BsSel select_pass(bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
+static BsSel select_pass(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
 	const int L = plan->limbs, fmax = pass_fmax(pass);
 	// variant 4: every pass on register tiles; variant 5 (mixed): register tiles for the passes whose
 	// twiddles all lie in GF(2^8) (their kernel fits four waves per SIMD), LDS tiles for the others
@@ -853,11 +687,12 @@ static int print_trace(int i, const BsSel& sel, int fmax, const unsigned long lo
 	return BN_OK;
 }
 
-static int launch_one(bn_antt_plan* plan, const BsPass& pass, int i, const uint32_t* d_in, uint32_t* d_out,
-                      size_t batch, hipStream_t st, const BsDevKnobs& kn) {
+static int launch_one(bn_antt_plan* plan, int i, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st,
+                      const BsDevKnobs& kn) {
+	const BsPass& pass = plan->passes[i];
 	const size_t ntiles = (batch << plan->log_rate) << pass.n_outer;
 	const BsSel sel = select_pass(plan, pass, ntiles, kn);
-	if (sel.rr) return rr_launch_pass(plan, i, d_in, d_out, batch, st);
+	if (sel.rr) return rr_launch_pass(plan, i, plan->rt[i], sel.kernel, ntiles, kn, d_in, d_out, st);
 	if (!sel.kernel) BN_FAIL(BN_ERR_UNSUPPORTED, "variant %d has no bitsliced passes", plan->variant);
 	BsParams prm;
 	prm.src = d_in;
@@ -887,86 +722,20 @@ static int launch_one(bn_antt_plan* plan, const BsPass& pass, int i, const uint3
 
 // the kernel pass i launches under the plan's variant (variants 1, 4, 5), nullptr otherwise
 const void* bs_pass_kernel(bn_antt_plan* plan, int i) {
-	size_t n_passes = 0;
-	const BsPass* passes = bs_passes(plan, &n_passes);
-	if (i < 0 || (size_t)i >= n_passes) return nullptr;
+	if (i < 0 || (size_t)i >= plan->passes.size()) return nullptr;
 	// the kernel for ONE transform (bench / profiles): a batched launch of the same pass may pick
 	// another (the lane-split and small-bottom kernels depend on the tile count)
-	const size_t ntiles = ((size_t)1 << plan->log_rate) << passes[i].n_outer;
-	return select_pass(plan, passes[i], ntiles, dev_knobs()).kernel;
+	const BsPass& pass = plan->passes[i];
+	const size_t ntiles = ((size_t)1 << plan->log_rate) << pass.n_outer;
+	return select_pass(plan, pass, ntiles, dev_knobs()).kernel;
 }
 
 int launch_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st) {
-	size_t n_passes = 0;
-	const BsPass* passes = bs_passes(plan, &n_passes);
 	const BsDevKnobs kn = dev_knobs();
-	for (size_t i = 0; i < n_passes; i++) {
-		int rc = launch_one(plan, passes[i], (int)i, d_in, d_out, batch, st, kn);
+	for (size_t i = 0; i < plan->passes.size(); i++) {
+		int rc = launch_one(plan, (int)i, d_in, d_out, batch, st, kn);
 		if (rc != BN_OK) return rc;
 	}
-	return BN_OK;
-}
-
-// lane bits that lane coordinate c_k depends on
-static const int kCoordDeps[6][2] = {{0, 2}, {1, 2}, {2, -1}, {3, -1}, {4, -1}, {5, -1}};
-
-// Sub-field class of stage j of a pass for the register-tile block stages: the smallest of 0 (every
-// twiddle of the stage is zero), 2, 4 bits that holds every contribution of the stage (tile, outer
-// and coset bits: a twiddle is an XOR of them), else the pass's own 8 / 16 / 32 (BsPass::field)
-static int rt_stage_class(const BsPass& p, int j) {
-	uint32_t acc = 0;
-	for (int m = 0; m < kBlkBits; m++) acc |= p.twt[j][m];
-	for (int m = 0; m < kMaxOuter; m++) acc |= p.two[j][m];
-	for (int c = 0; c < kMaxRateBits; c++) acc |= p.twc[j][c];
-	return acc == 0 ? 0 : acc < 4u ? 2 : acc < 16u ? 4 : p.field[j];
-}
-
-int make_rt(const BsPass& p, bool bottom, RtPass* out) {
-	RtPass r;
-	memset(&r, 0, sizeof r);
-	r.lo = p.lo;
-	r.k = p.k;
-	r.role = p.role;
-	r.n_outer = p.n_outer;
-	memcpy(r.bb, p.bb, sizeof r.bb);
-	memcpy(r.ob, p.ob, sizeof r.ob);
-	memcpy(r.two, p.two, sizeof r.two);
-	memcpy(r.twc, p.twc, sizeof r.twc);
-	for (int m = 0; m < kBlkBits; m++) r.jm[m] = -1;
-	for (int j = 0; j < p.k; j++)
-		if (p.stage_m[j] >= 0) {
-			r.jm[p.stage_m[j]] = j;
-			r.field_m[p.stage_m[j]] = rt_stage_class(p, j);
-		}
-	r.mlow = kBlkBits;
-	for (int m = 0; m < kBlkBits; m++)
-		if (r.jm[m] >= 0) r.mlow = std::min(r.mlow, m);
-	// the stage bits must be the top tile bits (stages run from tile bit 6 down)
-	for (int m = r.mlow; m < kBlkBits; m++)
-		if (r.jm[m] < 0) return BN_ERR_UNSUPPORTED;
-	if (bottom && r.mlow != 0) return BN_ERR_UNSUPPORTED;
-	auto add_coords = [&](uint32_t* tau, int kmin, const uint32_t* twt) {
-		for (int k = kmin; k < 6; k++)
-			for (int b : kCoordDeps[k])
-				if (b >= 0) tau[b] ^= twt[k + 1];
-	};
-	for (int m = r.mlow; m < kBlkBits; m++) add_coords(r.tau[m], m, p.twt[r.jm[m]]);
-	if (bottom) {
-		for (int s = 0; s < 5; s++) {
-			const int j = s - p.lo;
-			r.field_s[s] = p.field[j];
-			r.cb_const[s] = p.twt[j][0];
-			add_coords(r.tau_iw[s], 0, p.twt[j]);
-			for (int i = 0; i < 32; i++) {
-				// p.pat folds the variant-1 block difference (tile bit 6); fold tile bit 0 instead
-				uint32_t v = p.pat[s][i];
-				if ((p.twt[j][kBlkBits - 1] >> i) & 1) v ^= ~lane_mask(s);
-				if ((p.twt[j][0] >> i) & 1) v ^= ~lane_mask(s);
-				r.pat[s][i] = v;
-			}
-		}
-	}
-	*out = r;
 	return BN_OK;
 }
 
@@ -976,8 +745,7 @@ int make_rt(const BsPass& p, bool bottom, RtPass* out) {
 // pass does not depend on the values (bitwise arithmetic, no data-dependent control flow).
 int bs_time_passes(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, int reps,
                    hipStream_t st, float* ms, int max_passes, int* n_out) {
-	size_t n_passes = 0;
-	const BsPass* passes = bs_passes(plan, &n_passes);
+	const int n_passes = (int)plan->passes.size();
 	BsDevKnobs kn = dev_knobs();
 	kn.trace = false;
 	const int saved = plan->timing;
@@ -985,42 +753,23 @@ int bs_time_passes(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, si
 	hipEvent_t e0 = nullptr, e1 = nullptr;
 	int rc = BN_OK;
 	if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = BN_ERR_HIP;
-	for (size_t i = 0; rc == BN_OK && i < n_passes; i++) {
+	for (int i = 0; rc == BN_OK && i < n_passes; i++) {
 		// one untimed launch first: the pass's input is then the steady-state layout
-		rc = launch_one(plan, passes[i], (int)i, d_in, d_out, batch, st, kn);
+		rc = launch_one(plan, i, d_in, d_out, batch, st, kn);
 		if (rc == BN_OK && hipEventRecord(e0, st) != hipSuccess) rc = BN_ERR_HIP;
-		for (int r = 0; rc == BN_OK && r < reps; r++) rc = launch_one(plan, passes[i], (int)i, d_in, d_out, batch, st, kn);
+		for (int r = 0; rc == BN_OK && r < reps; r++) rc = launch_one(plan, i, d_in, d_out, batch, st, kn);
 		if (rc == BN_OK && hipEventRecord(e1, st) != hipSuccess) rc = BN_ERR_HIP;
 		float t = 0.f;
 		if (rc == BN_OK && (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess))
 			rc = BN_ERR_HIP;
-		if (rc == BN_OK && (int)i < max_passes) ms[i] = t / (float)reps;
+		if (rc == BN_OK && i < max_passes) ms[i] = t / (float)reps;
 	}
 	if (e0) (void)hipEventDestroy(e0);
 	if (e1) (void)hipEventDestroy(e1);
 	plan->timing = saved;
 	if (rc != BN_OK) BN_FAIL(rc, "timing the passes failed");
-	*n_out = (int)n_passes;
+	*n_out = n_passes;
 	return BN_OK;
 }
 
 }  // namespace bn
-
-// Host only (no plan, no device): the sub-field class the register-tile table carries for every
-// stage of the upper passes, out[s - 12] for stage s = 12 .. log_h - 1.
-extern "C" int bn_antt_stage_classes(int log_h, int log_rate, int32_t* out, size_t n) {
-	using namespace bn;
-	BN_CHECK_ARG(out != nullptr, "output pointer is NULL");
-	BN_CHECK_ARG(log_rate >= 0 && log_rate <= 4 && log_h + log_rate <= 32, "log_h + log_rate must be <= 32, log_rate in [0,4]");
-	bn_antt_plan plan;
-	plan.log_h = log_h;
-	plan.log_rate = log_rate;
-	plan.width = log_h + log_rate - 1;
-	if (!bs_supports(&plan)) BN_FAIL(BN_ERR_UNSUPPORTED, "the bitsliced passes need log_h >= %d", kMinLogH);
-	BN_CHECK_ARG(n >= (size_t)(log_h - kMinLogH), "output holds %zu entries, need %d", n, log_h - kMinLogH);
-	subspace_evals(log_h, log_rate, plan.s_host);
-	const std::vector<BsPass> passes = plan_passes(&plan);
-	for (size_t i = 0; i + 1 < passes.size(); i++)
-		for (int j = 0; j < passes[i].k; j++) out[passes[i].lo + j - kMinLogH] = rt_stage_class(passes[i], j);
-	return BN_OK;
-}

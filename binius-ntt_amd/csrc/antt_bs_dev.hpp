@@ -29,11 +29,6 @@ __device__ __forceinline__ void st_stream(uint32_t* p, uint4 g) {
 	__builtin_nontemporal_store(v, (u32x4*)p);
 }
 
-// bit masks of the bit-lanes p with bit j of p set
-__host__ __device__ constexpr uint32_t lane_mask(int j) {
-	return j == 0 ? 0xAAAAAAAAu : j == 1 ? 0xCCCCCCCCu : j == 2 ? 0xF0F0F0F0u : j == 3 ? 0xFF00FF00u : 0xFFFF0000u;
-}
-
 // out = w*x for 32 bitsliced GF(2^32) limbs (alias-safe: out may be x). W holds bit i of each
 // lane's twiddle in word i; `field` (uniform per stage) selects the sub-field circuit, FMAX (the
 // largest field of the pass) removes the circuits a pass never uses.

@@ -247,36 +247,24 @@ static int fold_check(const bn_antt_plan* p, int round, int arity, const uint32_
 
 extern "C" int bn_antt_fri_fold_device(bn_antt_plan* p, const void* d_in, void* d_out, int round, int arity,
                                        const uint32_t* challenges, size_t batch, void* stream) {
-	int rc = fold_check(p, round, arity, challenges);
-	if (rc != BN_OK) return rc;
-	BN_CHECK_ARG(d_in != nullptr && d_out != nullptr, "device buffers must be non-NULL");
-	BN_CHECK_ARG(batch >= 1, "batch must be >= 1");
+	if (int rc = fold_check(p, round, arity, challenges)) return rc;
+	if (int rc = check_device_args(p, d_in, d_out, batch)) return rc;
 	const int log_in = p->log_h + p->log_rate - round;
 	BN_CHECK_ARG(batch <= (((size_t)1 << 40) >> log_in), "batch of %zu codewords is too large", batch);
 	const size_t in_bytes = (batch << log_in) * 16;
-	const size_t out_bytes = in_bytes >> arity;
-	const char* a = (const char*)d_in;
-	const char* b = (const char*)d_out;
-	BN_CHECK_ARG(a + in_bytes <= b || b + out_bytes <= a, "d_in and d_out must not overlap");
-	int dev_prev = 0;
-	(void)hipGetDevice(&dev_prev);
-	if (dev_prev != p->device) BN_HIP(hipSetDevice(p->device));
-	rc = launch_fold(p, d_in, d_out, round, arity, challenges, batch, (hipStream_t)stream);
-	if (dev_prev != p->device) (void)hipSetDevice(dev_prev);
-	return rc;
+	if (int rc = check_no_overlap(d_in, in_bytes, d_out, in_bytes >> arity)) return rc;
+	BN_DEVICE_SCOPE(p->device);
+	return launch_fold(p, d_in, d_out, round, arity, challenges, batch, (hipStream_t)stream);
 }
 
 extern "C" int bn_antt_fri_fold_host(bn_antt_plan* p, const void* in, size_t in_elems, int round, int arity,
                                      const uint32_t* challenges, void* out) {
-	int rc = fold_check(p, round, arity, challenges);
-	if (rc != BN_OK) return rc;
+	if (int rc = fold_check(p, round, arity, challenges)) return rc;
 	BN_CHECK_ARG(in != nullptr && out != nullptr, "host buffers must be non-NULL");
 	const int log_in = p->log_h + p->log_rate - round;
 	BN_CHECK_ARG(in_elems == ((size_t)1 << log_in), "input has %zu elements, round %d of the plan has 2^%d", in_elems, round,
 	             log_in);
-	int dev_prev = 0;
-	(void)hipGetDevice(&dev_prev);
-	BN_HIP(hipSetDevice(p->device));
+	BN_DEVICE_SCOPE(p->device);
 	const size_t in_bytes = in_elems * 16;
 	const size_t out_bytes = in_bytes >> arity;
 	if (!p->own_stream) BN_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
@@ -284,13 +272,13 @@ extern "C" int bn_antt_fri_fold_host(bn_antt_plan* p, const void* in, size_t in_
 	void* d_src = nullptr;
 	BN_HIP(hipMalloc(&d_src, in_bytes + out_bytes));
 	void* d_dst = (char*)d_src + in_bytes;
+	int rc = BN_OK;
 	hipError_t e = hipMemcpyAsync(d_src, in, in_bytes, hipMemcpyHostToDevice, p->own_stream);
 	if (e == hipSuccess) rc = launch_fold(p, d_src, d_dst, round, arity, challenges, 1, p->own_stream);
 	if (e == hipSuccess && rc == BN_OK) e = hipMemcpyAsync(out, d_dst, out_bytes, hipMemcpyDeviceToHost, p->own_stream);
 	const hipError_t es = hipStreamSynchronize(p->own_stream);
 	if (e == hipSuccess) e = es;
-	(void)hipFree(d_src);
-	(void)hipSetDevice(dev_prev);
+	(void)hipFree(d_src);  // on every path: nothing above returns between the allocation and here
 	if (rc != BN_OK) return rc;
 	if (e != hipSuccess) BN_FAIL(BN_ERR_HIP, "host fold failed: %s", hipGetErrorString(e));
 	return BN_OK;

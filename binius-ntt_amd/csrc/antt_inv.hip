@@ -204,8 +204,8 @@ static const void* inv_kernel_for(int L, int role, int fmax) {
 }
 
 int launch_inv_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, int coset, size_t batch, hipStream_t st) {
-	size_t n_passes = 0;
-	const BsPass* passes = bs_passes(plan, &n_passes);
+	const std::vector<BsPass>& passes = plan->passes;
+	const size_t n_passes = passes.size();
 	const int L = plan->limbs;
 	if (!plan->inv_prepared) {
 		for (int role = 0; role < 4; role++)

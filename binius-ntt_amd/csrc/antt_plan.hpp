@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "antt_passes.hpp"
 #include "common.hpp"
 
 struct bn_antt_plan {
@@ -19,9 +20,10 @@ struct bn_antt_plan {
 	int num_cus = 0; // compute units of the device (launches below two tiles per CU pick other kernels)
 	std::vector<uint32_t> s_host;  // log_h x width, row-major
 	uint32_t* s_dev = nullptr;     // same on the device
-	uint32_t* scratch = nullptr;   // pass-intermediate buffer (variant-specific)
-	size_t scratch_bytes = 0;
-	std::vector<unsigned char> bs_passes;  // variant-1 pass tables (antt_bs.hip), built on first use
+	// pass tables of the bitsliced kernels and the register-tile table of every pass (antt_passes.cpp),
+	// filled once by bs_prepare; empty for variant-0 plans
+	std::vector<bn::BsPass> passes;
+	std::vector<bn::RtPass> rt;
 	int inv_prepared = 0;  // LDS attribute of the bitsliced inverse kernels set (antt_inv.hip)
 	hipStream_t own_stream = nullptr;
 	// host-apply staging
@@ -42,8 +44,21 @@ struct bn_antt_plan {
 };
 
 namespace bn {
-// precompute_subspace_evals (src/ulvt/ntt/additive_ntt.cuh:273-309), GF(2^32) values.
-void subspace_evals(int log_h, int log_rate, std::vector<uint32_t>& s);
+// The argument checks of every *_device entry point (forward, inverse, fold): the plan, the buffers
+// and the batch, then (after the checks a call adds of its own) that the bytes read and the bytes
+// written do not overlap.
+inline int check_device_args(const bn_antt_plan* p, const void* d_in, const void* d_out, size_t batch) {
+	BN_CHECK_ARG(p != nullptr, "plan is NULL");
+	BN_CHECK_ARG(d_in != nullptr && d_out != nullptr, "device buffers must be non-NULL");
+	BN_CHECK_ARG(batch >= 1, "batch must be >= 1");
+	return BN_OK;
+}
+inline int check_no_overlap(const void* d_in, size_t in_bytes, const void* d_out, size_t out_bytes) {
+	const char* a = (const char*)d_in;
+	const char* b = (const char*)d_out;
+	BN_CHECK_ARG(a + in_bytes <= b || b + out_bytes <= a, "d_in and d_out must not overlap");
+	return BN_OK;
+}
 // hipEvent timing around one launch of pass `kind` (no-op unless plan->timing).
 int timing_begin(bn_antt_plan* p, int kind, hipStream_t st);
 int timing_end(bn_antt_plan* p, int kind, hipStream_t st);

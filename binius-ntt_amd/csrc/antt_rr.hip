@@ -404,39 +404,33 @@ int rr_prepare(bn_antt_plan* plan) {
 	return BN_OK;
 }
 
-// The kernel of a pass over `ntiles` tiles. The bottom pass of a launch with fewer tiles than two
-// per CU runs one wave per SIMD whatever its register count, so it takes the instance compiled
-// without the three-waves bound.
-const void* rr_pass_kernel(bn_antt_plan* plan, const BsPass& pass, size_t ntiles) {
+// The kernel of a pass over `ntiles` tiles. The bottom pass of a small launch runs one wave per SIMD
+// whatever its register count, so it takes the instance compiled without the three-waves bound.
+const void* rr_pass_kernel(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles) {
 	const int fmax = pass_fmax(pass);
-	if (plan->limbs == 4 && pass.role == ROLE_LAST && ntiles < (size_t)2 * (size_t)plan->num_cus) return rr::kernel_small_last(fmax);
+	if (plan->limbs == 4 && pass.role == ROLE_LAST && small_launch(plan, ntiles)) return rr::kernel_small_last(fmax);
 	return rr::kernel_for(plan->limbs, pass.role, fmax);
 }
 
-// pass i of variant 4 (same pass split and tables as variant 1)
-int rr_launch_pass(bn_antt_plan* plan, int i, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st) {
-	size_t n_passes = 0;
-	const BsPass* passes = bs_passes(plan, &n_passes);
-	if (i < 0 || (size_t)i >= n_passes) BN_FAIL(BN_ERR_INVALID, "pass %d out of range", i);
-	const BsPass& pass = passes[i];
-	const bool bottom = pass.role == ROLE_LAST || pass.role == ROLE_SINGLE;
+// pass i of variant 4 (same pass split as variant 1, the plan's register-tile table of it)
+int rr_launch_pass(bn_antt_plan* plan, int i, const RtPass& rt, const void* kernel, size_t ntiles, const BsDevKnobs& kn,
+                   const uint32_t* d_in, uint32_t* d_out, hipStream_t st) {
 	rr::RrParams prm;
 	prm.src = d_in;
 	prm.dst = d_out;
 	prm.log_h = plan->log_h;
 	prm.log_rate = plan->log_rate;
+	prm.p = rt;
 #ifdef BN_DEV
-	prm.dbg = 0;
-	if (const char* e = getenv("BN_DEBUG_FLAGS")) prm.dbg = atoi(e) & 3;
+	prm.dbg = kn.dbg & 3;
+#else
+	(void)kn;
 #endif
-	int rc = make_rt(pass, bottom, &prm.p);
-	if (rc != BN_OK) BN_FAIL(rc, "register-tile pass table: stage bits are not the top tile bits");
 	const int L = plan->limbs;
-	const size_t ntiles = (batch << plan->log_rate) << pass.n_outer;
-	rc = timing_begin(plan, i, st);
+	int rc = timing_begin(plan, i, st);
 	if (rc != BN_OK) return rc;
 	void* args[] = {&prm};
-	BN_HIP(hipLaunchKernel(rr_pass_kernel(plan, pass, ntiles), dim3((unsigned)ntiles), dim3(64 * L), args, rr::lds_bytes(L), st));
+	BN_HIP(hipLaunchKernel(kernel, dim3((unsigned)ntiles), dim3(64 * L), args, rr::lds_bytes(L), st));
 	return timing_end(plan, i, st);
 }
 

@@ -183,18 +183,6 @@ __global__ __launch_bounds__(kT) void qm_fold(uint32_t* cols, size_t col_words, 
 	}
 }
 
-struct DevScope {
-	int prev = -1;
-	explicit DevScope(int d) {
-		if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-		if (prev != d) (void)hipSetDevice(d);
-	}
-	~DevScope() {
-		int cur = -1;
-		if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-	}
-};
-
 static unsigned grid_for(const bn_qm31_sumcheck* S, size_t items) {
 	const size_t want = (items + kT - 1) / kT;
 	return (unsigned)std::max<size_t>(1, std::min<size_t>(want, (size_t)S->cus * S->wg_per_cu));
@@ -213,7 +201,7 @@ extern "C" int bn_qm31_sumcheck_create(int device, int num_vars, const uint32_t*
 	int ndev = 0;
 	BN_HIP(hipGetDeviceCount(&ndev));
 	BN_CHECK_ARG(device >= 0 && device < ndev, "device %d out of range", device);
-	DevScope ds(device);
+	DeviceScope ds(device);
 	auto* S = new bn_qm31_sumcheck();
 	S->device = device;
 	S->num_vars = num_vars;
@@ -259,7 +247,7 @@ static int apply_pending(bn_qm31_sumcheck* S) {
 extern "C" int bn_qm31_sumcheck_round_messages(bn_qm31_sumcheck* S, uint32_t* points) {
 	BN_CHECK_ARG(S != nullptr && points != nullptr, "NULL argument");
 	BN_CHECK_ARG(S->round < S->num_vars, "all %d rounds are done", S->num_vars);
-	DevScope ds(S->device);
+	DeviceScope ds(S->device);
 	const size_t h = S->cur / 2, col_words = ((size_t)4) << S->num_vars;
 	unsigned long long* acc = S->acc + 12 * S->par;
 	unsigned long long* clr = S->acc + 12 * (1 - S->par);
@@ -283,7 +271,7 @@ extern "C" int bn_qm31_sumcheck_round_messages(bn_qm31_sumcheck* S, uint32_t* po
 extern "C" int bn_qm31_sumcheck_fold(bn_qm31_sumcheck* S, const uint32_t* challenge) {
 	BN_CHECK_ARG(S != nullptr && challenge != nullptr, "NULL argument");
 	BN_CHECK_ARG(S->round < S->num_vars, "all %d rounds are done", S->num_vars);
-	DevScope ds(S->device);
+	DeviceScope ds(S->device);
 	const size_t h = S->cur / 2;
 	if (int rc = apply_pending(S)) return rc;
 	// deferred: the next round_messages fuses it (qm_fold_messages); final_values applies it alone
@@ -298,7 +286,7 @@ extern "C" int bn_qm31_sumcheck_fold(bn_qm31_sumcheck* S, const uint32_t* challe
 extern "C" int bn_qm31_sumcheck_final_values(bn_qm31_sumcheck* S, uint32_t* out /* 8 words */) {
 	BN_CHECK_ARG(S != nullptr && out != nullptr, "NULL argument");
 	BN_CHECK_ARG(S->round == S->num_vars, "only after all %d rounds (at round %d)", S->num_vars, S->round);
-	DevScope ds(S->device);
+	DeviceScope ds(S->device);
 	const size_t col_words = ((size_t)4) << S->num_vars;
 	if (int rc = apply_pending(S)) return rc;
 	BN_HIP(hipMemcpyAsync(out, S->cols, 16, hipMemcpyDeviceToHost, S->stream));
@@ -309,7 +297,7 @@ extern "C" int bn_qm31_sumcheck_final_values(bn_qm31_sumcheck* S, uint32_t* out 
 
 extern "C" int bn_qm31_sumcheck_destroy(bn_qm31_sumcheck* S) {
 	if (!S) return BN_OK;
-	DevScope ds(S->device);
+	DeviceScope ds(S->device);
 	if (S->stream) (void)hipStreamSynchronize(S->stream);
 	if (S->cols) (void)hipFree(S->cols);
 	if (S->acc) (void)hipFree(S->acc);

@@ -708,19 +708,6 @@ size_t srv_lds_bytes() { return ((size_t)kSrvGroups * Grp<kSrvG>::kSlotWords + 1
 template <int G>
 size_t lds_bytes() { return ((size_t)Grp<G>::kSlotsWords + 128 + 8 * (kMaxD + 1) + 1) * sizeof(uint32_t); }
 
-struct DeviceScope {
-	int prev = -1;
-	bool ok = true;
-	explicit DeviceScope(int dev) {
-		if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-		if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-	}
-	~DeviceScope() {
-		int cur = -1;
-		if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-	}
-};
-
 }  // namespace
 }  // namespace bn
 
@@ -1072,8 +1059,7 @@ static int create_from_host(int device, int num_vars, int d, int transposed, con
 	BN_CHECK_ARG(evals, "NULL evals");
 	int rc = check_shape(num_vars, d, transposed);
 	if (rc != BN_OK) return rc;
-	DeviceScope ds(device);
-	if (!ds.ok) BN_FAIL(BN_ERR_HIP, "hipSetDevice(%d) failed", device);
+	BN_DEVICE_SCOPE(device);
 	bn_sumcheck* sc = new bn_sumcheck;
 	sc->device = device;
 	sc->num_vars = num_vars;
@@ -1125,8 +1111,7 @@ extern "C" int bn_sumcheck_create_device(int device, int num_vars, int d, int tr
 	BN_CHECK_ARG(d_evals, "NULL evals");
 	int rc = check_shape(num_vars, d, transposed);
 	if (rc != BN_OK) return rc;
-	DeviceScope ds(device);
-	if (!ds.ok) BN_FAIL(BN_ERR_HIP, "hipSetDevice(%d) failed", device);
+	BN_DEVICE_SCOPE(device);
 	bn_sumcheck* sc = new bn_sumcheck;
 	sc->device = device;
 	sc->num_vars = num_vars;
@@ -1205,8 +1190,7 @@ extern "C" int bn_sumcheck_create_shard_device(int device, int num_vars, int d, 
 	BN_CHECK_ARG(rank >= 0 && rank < world, "rank out of range");
 	const size_t n = (size_t)1 << num_vars;
 	BN_CHECK_ARG(n >= (size_t)32 * world, "need at least one 32-element batch per rank");
-	DeviceScope ds(device);
-	if (!ds.ok) BN_FAIL(BN_ERR_HIP, "hipSetDevice(%d) failed", device);
+	BN_DEVICE_SCOPE(device);
 	bn_sumcheck* sc = new bn_sumcheck;
 	sc->device = device;
 	sc->num_vars = num_vars;

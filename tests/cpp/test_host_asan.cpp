@@ -289,6 +289,42 @@ static void library_host_checks() {
 	}
 	check(ok, "library bn_sumcheck_interpolate vs oracle");
 
+	// the host-only pass planner (csrc/antt_passes.cpp) over every size it plans: log_h 12..28 x
+	// log_rate 0..4, each output in a heap allocation of exactly the size the call asks for
+	{
+		uint32_t probe[512];
+		check(bn_antt_inword_tables(12, 0, probe, 512) == BN_OK && probe[0] <= 512, "bn_antt_inword_tables reports its size");
+		const size_t words = probe[0];
+		bool tabs = true, classes = true;
+		for (int log_h = 12; log_h <= 28; log_h++)
+			for (int r = 0; r <= 4; r++) {
+				std::vector<uint32_t> t(words);
+				tabs = tabs && bn_antt_inword_tables(log_h, r, t.data(), t.size()) == BN_OK && t[0] == words &&
+				       (int)t[4] == log_h - 12;  // the bottom pass fixes every index bit above its tile
+				for (int s = 0; s < 5 && tabs; s++) {
+					const uint32_t f = t[5 + t[2] + (s + 1) * (32 + t[1] + t[2] + t[3] + 1) - 1];
+					tabs = f == 8 || f == 16 || f == 32;
+				}
+				const size_t n = (size_t)(log_h - 12);
+				std::vector<int32_t> c(n ? n : 1, -1);  // n == 0: nothing is written, the pointer must still be non-NULL
+				classes = classes && bn_antt_stage_classes(log_h, r, c.data(), n) == BN_OK;
+				for (size_t i = 0; i < n; i++)
+					classes = classes && (c[i] == 0 || c[i] == 2 || c[i] == 4 || c[i] == 8 || c[i] == 16 || c[i] == 32);
+			}
+		check(tabs, "bn_antt_inword_tables, log_h 12..28 x log_rate 0..4");
+		check(classes, "bn_antt_stage_classes, log_h 12..28 x log_rate 0..4");
+		std::vector<uint32_t> t(words);
+		std::vector<int32_t> c(4);
+		check(bn_antt_inword_tables(11, 0, t.data(), t.size()) == BN_ERR_UNSUPPORTED, "bn_antt_inword_tables rejects log_h 11");
+		check(bn_antt_inword_tables(12, 0, t.data(), 10) == BN_ERR_INVALID, "bn_antt_inword_tables rejects a short output");
+		check(bn_antt_inword_tables(12, 5, t.data(), t.size()) == BN_ERR_INVALID, "bn_antt_inword_tables rejects log_rate 5");
+		check(bn_antt_inword_tables(12, 0, nullptr, t.size()) == BN_ERR_INVALID, "bn_antt_inword_tables rejects a NULL output");
+		check(bn_antt_stage_classes(11, 0, c.data(), 4) == BN_ERR_UNSUPPORTED, "bn_antt_stage_classes rejects log_h 11");
+		check(bn_antt_stage_classes(16, 0, c.data(), 3) == BN_ERR_INVALID, "bn_antt_stage_classes rejects a short output");
+		check(bn_antt_stage_classes(16, 5, c.data(), 4) == BN_ERR_INVALID, "bn_antt_stage_classes rejects log_rate 5");
+		check(bn_antt_stage_classes(16, 0, nullptr, 4) == BN_ERR_INVALID, "bn_antt_stage_classes rejects a NULL output");
+	}
+
 	// error paths: invalid arguments are rejected before any device call; with no device the
 	// device-touching calls fail with a status code (never abort), and bn_last_error says why
 	bn_antt_plan* plan = reinterpret_cast<bn_antt_plan*>(&ok);

@@ -174,6 +174,115 @@ def test_gf128_2p26_limb_md5_and_oracle(ntt_md5, dev):
     assert np.array_equal(y, want)
 
 
+def test_one_plan_across_small_and_full_launches(dev):
+    # One plan, launches on both sides of "fewer tiles than two per CU": at log_h 13 each of the two
+    # passes has 2 tiles per transform, so batch = num_cus is the first batch at which both leave the
+    # small-launch kernels. The plan's pass tables (the register-tile table of pass 0 among them) are
+    # built once and serve every call; what pass_kernel_name reports is the one-transform kernel and
+    # does not move with the batch of the calls in between.
+    import re
+    import torch
+    log_h = 13
+    n = 1 << log_h
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    ntt = B.AdditiveNTT(B.AdditiveNTTConf(log_h, 0, B.FanPaarTowerField(7)))
+    assert ntt.variant() == 5
+    names = [ntt.pass_kernel_name(0), ntt.pass_kernel_name(1)]
+    assert re.search(r"antt_rr_pass<4, 0, 8, 1>", names[0]), names  # the first pass is on register tiles
+    assert re.search(r"antt_rr_pass<4, 2, \d+, 1>", names[1]), names  # one transform: the small bottom pass
+    with pytest.raises(B.BnError):
+        ntt.pass_kernel_name(2)
+    x1 = O.fill128(0xCAC4ED, 0x5EED0000, n)
+    want1 = O.antt128(x1, log_h, 0)
+    xs = O.fill128(0xCAC4EE, 0x5EED0001, cus << log_h).reshape(cus, n, 4)
+
+    def same_names():
+        return [ntt.pass_kernel_name(0), ntt.pass_kernel_name(1)] == names
+
+    assert np.array_equal(_run_device(ntt, x1.reshape(-1), dev).reshape(-1, 4), want1)
+    assert same_names()
+    ys = _run_device(ntt, xs.reshape(-1), dev, batch=cus).reshape(cus, n, 4)
+    for b in (0, 1, cus - 1):
+        assert np.array_equal(ys[b], O.antt128(xs[b], log_h, 0)), b
+    assert same_names()
+    assert np.array_equal(_run_device(ntt, x1.reshape(-1), dev).reshape(-1, 4), want1)
+    assert same_names()
+
+
+def test_calls_leave_the_callers_current_device(dev):
+    """Every entry point of a plan on device 1 leaves the caller's current device (0) as it was, for
+    torch and for the HIP runtime the library itself is bound to, and computes what it should.
+    Skipped with fewer than two visible GPUs. Only successful calls and one call rejected for a bad
+    argument are made: the HIP error paths restore the device through the same scope object."""
+    import ctypes
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible GPUs")
+    from test_gpu_fri_fold import _ref_round
+    torch.cuda.set_device(0)
+    d1 = torch.device("cuda:1")
+
+    def on_device_0():
+        d = ctypes.c_int(-1)
+        assert B.lib().hipGetDevice(ctypes.byref(d)) == 0  # resolved through the library's own dependencies
+        return torch.cuda.current_device() == 0 and d.value == 0
+
+    def to_d1(a):
+        return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.int32)).to(d1)
+
+    def to_np(t):
+        torch.cuda.synchronize(d1)
+        return t.cpu().numpy().view(np.uint32).reshape(-1, 4)
+
+    log_h, r = 12, 1
+    n = 1 << log_h
+    x = O.fill128(0xD371CE, 0x5EED0000, n)
+    want = O.antt128(x, log_h, r)
+    ntt = B.AdditiveNTT(B.AdditiveNTTConf(log_h, r, B.FanPaarTowerField(7), device=1))
+    assert on_device_0()
+
+    y = torch.empty(4 * (n << r), dtype=torch.int32, device=d1)
+    ntt.forward_device(to_d1(x), y)
+    assert on_device_0()
+    assert np.array_equal(to_np(y), want)
+
+    out = B.NTTData(n << r, field_bits=128)
+    assert ntt.apply(B.NTTData(n, B.DataOrder.IN_ORDER, 128, x), out)
+    assert on_device_0()
+    assert np.array_equal(out.data, want)
+
+    back = torch.empty(4 * n, dtype=torch.int32, device=d1)
+    ntt.inverse_device(to_d1(want[n:]), back, coset=1)
+    assert on_device_0()
+    assert np.array_equal(to_np(back), x)
+
+    out = B.NTTData(n, field_bits=128)
+    assert ntt.inverse(B.NTTData(n, B.DataOrder.IN_ORDER, 128, want[n:]), out, coset=1)
+    assert on_device_0()
+    assert np.array_equal(out.data, x)
+
+    rnd = 6  # a round-6 codeword: 2^7 elements, 64 pairs for the per-pair reference
+    state = O.fill128(0xD371CF, 0x5EED0000, 1 << (log_h + r - rnd))
+    ch = O.fill128(0xF01D0000, 0xC4A11E00, 1)
+    want_fold = _ref_round(state, ntt.subspace_evals(), log_h, r, rnd, ch[0])
+    folded = torch.empty(4 * (state.shape[0] >> 1), dtype=torch.int32, device=d1)
+    ntt.fri_fold_device(to_d1(state), folded, rnd, ch)
+    assert on_device_0()
+    assert np.array_equal(to_np(folded), want_fold)
+
+    out = B.NTTData(state.shape[0] >> 1, field_bits=128)
+    assert ntt.fri_fold(B.NTTData(state.shape[0], B.DataOrder.IN_ORDER, 128, state), out, rnd, ch)
+    assert on_device_0()
+    assert np.array_equal(out.data, want_fold)
+
+    with pytest.raises(B.BnError):
+        ntt.inverse_device(to_d1(want[n:]), back, coset=2)  # coset out of [0, 2^1)
+    assert on_device_0()
+
+    ntt.close()
+    assert on_device_0()
+
+
 # Kernel variants (DESIGN.md section 5.1): 1 LDS tiles, 4 register tiles on every pass, 5 (the
 # default for log_h >= 12) register tiles for the GF(2^8)-only passes and LDS tiles for the others.
 # Same passes and layouts; every one parity-green so the A/B numbers stay reproducible.

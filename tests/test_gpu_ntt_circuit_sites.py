@@ -13,7 +13,7 @@ two transforms and log_rate 1 so that the coset and outer parts of the twiddles 
   antt_bs_pass<4, 1, 32> over stages 12..15, and the bottom pass, whose top stage now has GF(2^32)
   twiddles and so takes the scalar branch (ntt_mul32_w).
 
-Which circuit a stage runs is decided by its twiddles' field (plan_passes, csrc/antt_bs.hip: the
+Which circuit a stage runs is decided by its twiddles' field (plan_passes, csrc/antt_passes.cpp: the
 smallest of GF(2^8), GF(2^16), GF(2^32) that holds every subspace evaluation of the stage); the
 tests assert those fields from the oracle's subspace evaluations, and the kernels of each plan by
 name.
