@@ -7,13 +7,10 @@
 #include <stdint.h>
 
 #include "bitsliced.hpp"
+#include "quad_words.hpp"  // kRowWords, kQuadWords, kHexWords, kWideWords, kMaxD
 
 namespace bn {
 namespace quad {
-
-constexpr int kRowWords = 36;    // LDS words per 32-word row (padding: bank spread)
-constexpr int kQuadWords = 304;  // LDS words per quad slot (8 padded rows + spread)
-constexpr int kMaxD = 8;
 
 // compiler ordering for LDS traffic between lanes of one wave (the hardware executes a wave's
 // LDS instructions in order)
@@ -69,11 +66,8 @@ __device__ __forceinline__ void sst(const Slot& S, int r, const uint32_t* x) { s
 // GF(2^128) product on a quad. On entry slot row l holds limb l of the first operand and row 4+l
 // limb l of the second — or, with B_SHARED, the second operand is the unswizzled 128-word B
 // shared by every quad (the fold's broadcast challenge). On exit row l holds limb l of the product.
-// skip_mid (development-build timing experiment only): the third circuit is replaced by its
-// operand sum, i.e. 8 instead of 12 circuits per product (wrong results; an upper bound on what a
-// 9-circuit Karatsuba top level could save in the kernels that call this).
 template <bool B_SHARED>
-__device__ __forceinline__ void quad_mul(const Slot& S, const uint32_t* B, int l, bool skip_mid = false) {
+__device__ __forceinline__ void quad_mul(const Slot& S, const uint32_t* B, int l) {
 	wsync();
 	const int ia = l & 1, jb = (l == 1 || l == 2) ? 1 : 0;
 	const int ra = 2 * ia, rb = 4 + 2 * jb;  // rows of a0 (a1 = ra + 1) and b0 (b1 = rb + 1)
@@ -119,12 +113,7 @@ __device__ __forceinline__ void quad_mul(const Slot& S, const uint32_t* B, int l
 	sst(S, 2 * l, z);
 	sst(S, 2 * l + 1, y);
 	__builtin_amdgcn_sched_barrier(0);
-	if (skip_mid) {
-#pragma unroll
-		for (int i = 0; i < 32; i++) x[i] = sa[i] ^ sb[i];
-	} else {
-		bsm5_mul(sa, sb, x);  // (a0+a1)(b0+b1)
-	}
+	bsm5_mul(sa, sb, x);  // (a0+a1)(b0+b1)
 	__builtin_amdgcn_sched_barrier(0);
 	sld(y, S, 2 * l + 1);
 #pragma unroll
@@ -155,8 +144,8 @@ __device__ __forceinline__ void quad_mul(const Slot& S, const uint32_t* B, int l
 //   lane s < 12: q = s / 3 (P_q = A_i B_j as in quad_mul), t = s % 3 (Karatsuba z0, z2, z1)
 //   lane s < 8 : P_{s/2} half s%2 (lo = z0 + z2, hi = z1 + z0 + z2 + alpha(z2))
 //   lane s < 4 : limb s of the product
-// Slot rows: 0-3 operand A, 4-7 operand B (then the P halves), 8-19 the z's, 20-23 alpha(z2).
-constexpr int kHexWords = 24 * kRowWords + 16;
+// Slot rows: 0-3 operand A, 4-7 operand B (then the P halves), 8-19 the z's, 20-23 alpha(z2)
+// (kHexWords).
 
 template <bool B_SHARED>
 __device__ __forceinline__ void hex_mul(const Slot& S, const uint32_t* B, int s) {
@@ -229,9 +218,8 @@ __device__ __forceinline__ void hex_mul(const Slot& S, const uint32_t* B, int s)
 //   lane s < 12: GF(2^32) product (q, t) = s: lo = z0 + z2, hi = z1 + z0 + z2 + alpha(z2) over its
 //                three GF(2^16) products, into hex_mul's z rows (and alpha(z2) for t = 1)
 //   then hex_mul's last two phases (P halves, limbs).
-// Slot: hex_mul's 24 rows, then 36 GF(2^16) products of 16 words at a 20-word stride.
-constexpr int kWideZ16 = 24 * kRowWords;
-constexpr int kWideWords = kWideZ16 + 36 * 20 + 16;
+// Slot: hex_mul's 24 rows, then 36 GF(2^16) products of 16 words at a 20-word stride (kWideZ16,
+// kWideWords).
 
 template <bool B_SHARED>
 __device__ __forceinline__ void wide_mul(const Slot& S, const uint32_t* B, int s) {

@@ -7,8 +7,9 @@
 //   * the C++ host mirror's host-only classes (FanPaarTowerField<H>, BitsliceUtils<W>, NTTData,
 //     AdditiveNTTConf, BB31, QM31/interpolate_at) against the oracle;
 //   * the library's host-side code: the generated bitsliced circuits behind multiply_unrolled<H>,
-//     the packed-subfield helpers, bn_sumcheck_interpolate, and the argument-checking / error paths
-//     of the C-ABI (no device present here: they must fail cleanly with a status code);
+//     the packed-subfield helpers, bn_sumcheck_interpolate, the sumcheck round planner
+//     (csrc/sc_rounds.cpp) over every round shape, and the argument-checking / error paths of the
+//     C-ABI (no device present here: they must fail cleanly with a status code);
 //   * all 14 generated circuits of csrc/bitsliced_gen.hpp, compiled into this program, through
 //     the conformance routine of circuit_conformance.hpp with a small trial count: every alias
 //     mode, every operand in a heap allocation of exactly its documented size, so a gate that
@@ -34,6 +35,7 @@
 #include "utils/common.hpp"
 #include "../../oracle/oracle.h"
 #include "circuit_conformance.hpp"
+#include "sc_rounds.hpp"
 
 static int failures = 0;
 static void check(bool ok, const char* what) {
@@ -232,6 +234,75 @@ static void mirror_checks() {
 	check(ok, "mirror QM31 interpolate_at vs oracle");
 }
 
+// The sumcheck round planner (csrc/sc_rounds.cpp, host only): every round shape the prover can
+// reach, then the hand-derived selections.
+static void sumcheck_planner_checks() {
+	using namespace bn;
+	const ScKnobs knobs;  // the product build's thresholds
+	bool cover = true, pair_ok = true, coal_ok = true, post_ok = true, lds_ok = true, kernel_ok = true, small_ok = true;
+	for (int k = 0; k <= 30; k++)
+		for (int d = 1; d <= 8; d++)
+			for (int fold = 0; fold <= 1; fold++)
+				for (int skip1 = 0; skip1 <= 1; skip1++) {
+					const size_t cur = (size_t)1 << k;
+					if (fold && cur < 2) continue;
+					const ScShape s = sc_shape(cur, d);
+					const ScLaunch L = sc_plan_launch(s, fold != 0, skip1, knobs);
+					cover = cover && L.grid >= 1 && (L.grid - 1) * L.per_wg < L.items && L.items <= L.grid * L.per_wg;
+					if (L.kernel == ScKernel::FoldPair) pair_ok = pair_ok && s.n_pairs % 32 == 0 && L.items >= kPairMinItems;
+					if (L.kernel == ScKernel::FoldCoal) coal_ok = coal_ok && s.n_pairs % 16 == 0;
+					post_ok = post_ok && (L.post != 0) == (L.grid <= 64) && L.post_kernel == (!fold && !L.post);
+					lds_ok = lds_ok && L.lds <= 160 * 1024 && L.lds <= sc_max_lds_bytes();
+					kernel_ok = kernel_ok && (int)L.kernel >= 0 && (int)L.kernel < kScKernelCount &&
+					            (fold ? L.kernel >= ScKernel::Fold0G16 : L.kernel <= ScKernel::Messages2G64);
+					// the small modes have one width each, and their kernel is the mode's
+					if (s.mode != 0)
+						small_ok = small_ok && L.kernel == (fold ? ScKernel::Fold1G16 : s.mode == 1 ? ScKernel::Messages1G64 : ScKernel::Messages2G64);
+					else
+						small_ok = small_ok && L.kernel != ScKernel::Fold1G16 && L.kernel != ScKernel::Messages1G64 && L.kernel != ScKernel::Messages2G64;
+				}
+	check(cover, "sumcheck planner: (grid - 1) * per_wg < items <= grid * per_wg, cur 2^0..2^30 x d 1..8");
+	check(pair_ok, "sumcheck planner: sc_fold_pair only with n_pairs % 32 == 0 and items >= kPairMinItems");
+	check(coal_ok, "sumcheck planner: sc_fold_coal only with n_pairs % 16 == 0");
+	check(post_ok, "sumcheck planner: in-kernel post exactly on grids <= 64, sc_post after the other messages");
+	check(lds_ok && srv_lds_bytes() <= 160 * 1024, "sumcheck planner: dynamic LDS within 160 KiB");
+	check(kernel_ok, "sumcheck planner: every selection is an instantiated kernel of its kind");
+	check(small_ok, "sumcheck planner: the small modes run their own fixed-width kernels, the big mode never does");
+
+	auto plan = [&](int log_cur, int d, bool fold, int skip1) { return sc_plan_launch(sc_shape((size_t)1 << log_cur, d), fold, skip1, knobs); };
+	ScLaunch L = plan(24, 3, true, 0);
+	check(L.kernel == ScKernel::FoldPair && L.grid == 6144 && L.lds == 69632, "sumcheck planner: (2^24, 3, fold) = pair, grid 6144, LDS 69632");
+	L = plan(24, 3, false, 0);
+	check(L.kernel == ScKernel::Messages0G4 && L.G == 4 && L.grid == 16384 && L.lds == 78628 && !L.post && L.post_kernel,
+	      "sumcheck planner: (2^24, 3, messages) = <0,4>, grid 16384, LDS 78628, sc_post follows");
+	L = plan(24, 3, false, 1);
+	check(L.kernel == ScKernel::Messages0G4 && L.grid == 12288, "sumcheck planner: (2^24, 3, messages, skip1) = grid 12288");
+	L = plan(18, 3, true, 0);
+	check(L.kernel == ScKernel::FoldCoal && L.grid == 192, "sumcheck planner: (2^18, 3, fold) = coal, grid 192");
+	L = plan(16, 3, true, 0);
+	check(L.kernel == ScKernel::Fold0G16 && L.G == 16 && L.grid == 192, "sumcheck planner: (2^16, 3, fold) = sc_fold<0,16>, grid 192");
+	L = plan(12, 3, false, 1);
+	check(L.kernel == ScKernel::Messages0G64 && L.G == 64 && L.grid == 48 && L.post && !L.post_kernel,
+	      "sumcheck planner: (2^12, 3, messages, skip1) = <0,64>, grid 48, in-kernel post");
+	L = plan(5, 8, false, 0);
+	check(L.kernel == ScKernel::Messages1G64 && L.grid == 3, "sumcheck planner: (32, 8, messages) = <1,64>, grid 3");
+	L = plan(5, 8, true, 0);
+	check(L.kernel == ScKernel::Fold1G16 && L.grid == 1, "sumcheck planner: (32, 8, fold) = sc_fold<1,16>, grid 1");
+	bool last = true;
+	for (int d = 1; d <= 8; d++) {
+		L = plan(0, d, false, 0);
+		last = last && L.kernel == ScKernel::Messages2G64 && L.grid == 1 && L.items == 1;
+	}
+	check(last, "sumcheck planner: (1, d, messages) = <2,64>, grid 1");
+	// development-build overrides stay inside the instantiated set: a big-mode fold pushed off the
+	// coalesced kernels runs on 16 lanes
+	ScKnobs dev;
+	dev.hex_max = 0;
+	dev.wide_max = 0;
+	L = sc_plan_launch(sc_shape(64 * 8, 3), true, 0, dev);
+	check(L.kernel == ScKernel::Fold0G16, "sumcheck planner: threshold overrides choose only among instantiated kernels");
+}
+
 static void library_host_checks() {
 	std::mt19937_64 rng(11);
 	check(bn_version() && std::strlen(bn_version()) > 0, "bn_version");
@@ -356,6 +427,7 @@ int main() {
 	oracle_checks();
 	mirror_checks();
 	library_host_checks();
+	sumcheck_planner_checks();
 	failures += conformance::run_all(2);
 	std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "PASSED", failures);
 	return failures ? 1 : 0;

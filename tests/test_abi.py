@@ -62,7 +62,12 @@ def test_product_library_has_no_experiment_kernels():
         blob = f.read()
     # positive control: kernel names are stored as plain text in this file, so a name that is
     # absent below is absent from the library and not merely compressed or bundled out of sight
-    for name in (b"antt_bs_pass", b"antt_rr_pass", b"k_gf128_mul_bs"):
+    # (sc_messagesILi0ELi4E: the mangled sc_messages<0, 4>, a kept sumcheck instantiation)
+    for name in (b"antt_bs_pass", b"antt_rr_pass", b"k_gf128_mul_bs", b"sc_messagesILi0ELi4E"):
         assert name in blob, name
     for name in (b"antt_bs_persist3", b"antt_rr_mid_pf", b"antt_rr_pass_persist", b"sc_fold_msgs"):
+        assert name not in blob, name
+    # sumcheck instantiations that no round shape selects (tests/cpp/test_host_asan.cpp sweeps the
+    # planner): sc_fold<2, *>, sc_fold<0, 4>, sc_messages<1, 4>, sc_messages<2, 16>
+    for name in (b"sc_foldILi2E", b"sc_foldILi0ELi4E", b"sc_messagesILi1ELi4E", b"sc_messagesILi2ELi16E"):
         assert name not in blob, name

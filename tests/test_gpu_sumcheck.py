@@ -31,7 +31,9 @@ def _transcript(sc, n, ch):
     return np.stack(sums), np.stack(pts)
 
 
-@pytest.mark.parametrize("n,d", [(1, 2), (3, 3), (5, 1), (5, 2), (6, 3), (8, 4), (10, 2), (9, 5)])
+# (7, 8) and (6, 7): the buffers sized by the degree bound 8 (accumulator rows, the sequence word's
+# offset, the LDS tail) at and next to it, on the round server and the small modes
+@pytest.mark.parametrize("n,d", [(1, 2), (3, 3), (5, 1), (5, 2), (6, 3), (8, 4), (10, 2), (9, 5), (7, 8), (6, 7)])
 @pytest.mark.parametrize("transposed", [0, 1])
 def test_sumcheck_transcript_matches_oracle(n, d, transposed, dev):
     if transposed and n < 5:
@@ -108,7 +110,9 @@ def test_sumcheck_protocol_checks(n, d, full_points, dev, monkeypatch):
     sc.close()
 
 
-@pytest.mark.parametrize("world,n,d", [(2, 8, 3), (4, 9, 2), (8, 10, 3)])
+# (2, 7, 8) and (2, 6, 1): a gathered replica has no round server, so the launched small-mode
+# kernels run at both ends of d
+@pytest.mark.parametrize("world,n,d", [(2, 8, 3), (4, 9, 2), (8, 10, 3), (2, 7, 8), (2, 6, 1)])
 def test_sharded_provers_match_unsharded(world, n, d, dev):
     # `world` shard provers on one GPU, combined exactly as binius_ntt_amd.distributed does
     ev, ch = _case(n, d, 500 + world)
@@ -250,7 +254,8 @@ def test_sumcheck_errors(dev):
         B.Sumcheck(6, 9, False, _rand(4 * 64 * 9, 1))  # composition size above 8
 
 
-@pytest.mark.parametrize("n,d,transposed", [(1, 1, 0), (4, 3, 0), (5, 2, 1), (9, 3, 0), (12, 4, 1), (13, 1, 1)])
+@pytest.mark.parametrize("n,d,transposed", [(1, 1, 0), (4, 3, 0), (5, 2, 1), (9, 3, 0), (12, 4, 1), (13, 1, 1),
+                                         (7, 8, 1)])  # d = 8 on the fold-only path
 def test_multilinear_composition_eval_matches_oracle(n, d, transposed, dev):
     # evaluate_multilinear_composition (verifier.cu:88-107) on the GPU vs the oracle
     ev, ch = _case(n, d, 900 + 10 * n + d)
