@@ -77,6 +77,8 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 	// single-pass kernel keeps the per-stage pack / multiply / unpack path: with the packed
 	// stages in its loop it spills 28 (L = 4) and 23 (L = 1) VGPRs against 9 and 5
 	constexpr bool packed = ROLE == ROLE_LAST;
+	static_assert(FMAX == 8 || FMAX == 32, "early_u_words is sized for the register use of these two instances");
+	constexpr int EARLY = early_u_words(ROLE, FMAX);
 	const BsPass& ps = P.p;
 	const int tid = threadIdx.x;
 	// wave w owns limb w of the tile for every stage: the waves never wait for each other
@@ -117,7 +119,8 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 	};
 
 	// ---- tile-bit stages (index bits >= 5), high to low. Lane = block pair of the wave's limb;
-	// only V and the twiddle are live during the multiply, U is read afterwards.
+	// V, the twiddle and the first EARLY words of U are live during the multiply, the other words of
+	// U are read afterwards.
 	// In the bottom pass of a transform of two and more passes the same code runs stages 4..0
 	// (index bits inside the word, `inw`) on the
 	// packed pair (X, Y) that the lane keeps in the slots of blocks lane and lane + 64 (see
@@ -136,11 +139,9 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 		uint32_t W[32], V[32], Pr[32], U[32];
 #pragma unroll
 		for (int i = 0; i < 32; i += 4) *(uint4*)(V + i) = *(const uint4*)(pv + i);
-		// with the small GF(2^8) circuits there are registers for U: request it before the multiply
-		if (FMAX <= 8) {
+		// the first EARLY words of U are requested next to V, ahead of the multiply
 #pragma unroll
-			for (int i = 0; i < 32; i += 4) *(uint4*)(U + i) = *(const uint4*)(pu + i);
-		}
+		for (int i = 0; i < EARLY; i += 4) *(uint4*)(U + i) = *(const uint4*)(pu + i);
 		// the stage on the top tile bit with a lane-independent twiddle: scalar twiddle side
 		const bool uni = top_stage_uniform<FMAX>(ps, j, m) && !inw && !(BS_DBG(P) & 4);
 		if (uni) {
@@ -193,7 +194,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 #pragma unroll
 			for (int i = 0; i < 32; i += 4) {
 				uint32_t Uw[4], X[4], Y[4];
-				*(uint4*)Uw = FMAX <= 8 ? *(const uint4*)(U + i) : *(const uint4*)(pu + i);
+				*(uint4*)Uw = i < EARLY ? *(const uint4*)(U + i) : *(const uint4*)(pu + i);
 #pragma unroll
 				for (int t = 0; t < 4; t++) {
 					const uint32_t x = Uw[t] ^ Pr[i + t], y = V[i + t] ^ x;
@@ -206,7 +207,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 		} else {
 #pragma unroll
 			for (int i = 0; i < 32; i += 4) {
-				uint4 u = FMAX <= 8 ? *(const uint4*)(U + i) : *(const uint4*)(pu + i);
+				uint4 u = i < EARLY ? *(const uint4*)(U + i) : *(const uint4*)(pu + i);
 				u.x ^= Pr[i];
 				u.y ^= Pr[i + 1];
 				u.z ^= Pr[i + 2];

@@ -54,6 +54,12 @@ constexpr int kLoads = kTileBlocks * 8 / 64;  // 16-byte global loads per lane p
 // stage and wave for the workgroup-uniform twiddle parts
 constexpr size_t tile_lds_bytes(int L) { return ((size_t)L * kPlane + (size_t)L * kMaxStages) * sizeof(uint32_t); }
 
+// Words of a block stage's U that a lane requests from LDS next to V, ahead of the multiply circuit, so
+// that their latency runs under it; the other words are read after the circuit. All 32 with the
+// small GF(2^8) circuits and in the bottom pass (209-210 VGPRs). The upper GF(2^32) kernels have room
+// for 16 (248-252 VGPRs): with 24 or 32 they reach 256 and spill.
+constexpr int early_u_words(int role, int fmax) { return fmax <= 8 || role == ROLE_LAST ? 32 : 16; }
+
 // Stage-to-stage ordering inside one wave: a wave's LDS operations execute in order, so only the
 // compiler must not move accesses across this point (the wait also bounds the LDS queue).
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
