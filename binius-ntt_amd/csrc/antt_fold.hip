@@ -24,7 +24,8 @@
 // thread and level). Nothing is built per pair from all log_h + log_rate bits.
 //
 // Products: t*v' is four table-leaf GF(2^32) products (dmul_t32<5>). x -> r*x is GF(2)-linear and r
-// is a launch constant, so each work-group tabulates it once per level: r * (e << 4n) for the 32
+// is a launch constant, so each work-group tabulates it once per level (gf128_rtab.hpp, shared with
+// the eq-indicator expansion): r * (e << 4n) for the 32
 // nibble positions n and the 16 nibble values e (8 KiB of LDS per level, built from 128 dmul128_t
 // products of r with the unit elements), and a product is the XOR of 32 16-byte LDS reads. The 16
 // entries of a nibble position are 256 consecutive bytes, one per bank group: lanes with equal
@@ -33,6 +34,7 @@
 
 #include "antt_plan.hpp"
 #include "field_dev.hpp"
+#include "gf128_rtab.hpp"
 
 namespace bn {
 
@@ -41,7 +43,7 @@ constexpr int kFoldTile = 1 << kFoldTileLog;
 constexpr int kFoldThreadsLog = 9;  // 8 waves: two work-groups a CU at up to 128 VGPRs share their tables of r
 constexpr int kFoldThreads = 1 << kFoldThreadsLog;
 constexpr int kFoldMaxArity = 8;
-constexpr int kFoldRTab = 32 * 16;                      // uint4 entries of one level's table of r
+constexpr int kFoldRTab = kRTabEntries;                 // uint4 entries of one level's table of r (gf128_rtab.hpp)
 constexpr int kFoldGf8 = (kGf8LdsBytes + 15) / 16;      // uint4 slots of the GF(2^8) tables
 constexpr int kFoldWgsPerCu = 2;                        // resident work-groups (128 VGPRs, LDS up to arity 6)
 
@@ -68,22 +70,6 @@ __device__ __forceinline__ uint32_t fold_tw_bits(const uint32_t* row, unsigned l
 	return w;
 }
 
-__device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }
-
-// r * x from the level's nibble table T[32][16]
-__device__ __forceinline__ uint4 fold_mul_r(const uint4* T, uint4 x) {
-	const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
-	uint4 acc = make_uint4(0, 0, 0, 0);
-#pragma unroll
-	for (int w = 0; w < 4; w++) {
-#pragma unroll
-		for (int nib = 0; nib < 8; nib++) acc = xor4(acc, T[(w * 8 + nib) * 16 + ((xs[w] >> (4 * nib)) & 15u)]);
-		// at most 16 reads (64 VGPRs) in flight: all 32 at once cost 185 VGPRs, half the waves
-		if (w & 1) asm volatile("" : "+v"(acc.x), "+v"(acc.y), "+v"(acc.z), "+v"(acc.w) : : "memory");
-	}
-	return acc;
-}
-
 // one pair: the inverse butterfly with twiddle t, then the two halves combined at r (table T)
 __device__ __forceinline__ uint4 fold_pair(uint4 u, uint4 v, uint32_t t, const uint4* T, const uint8_t* tab) {
 	v = xor4(v, u);
@@ -104,33 +90,15 @@ __global__ __launch_bounds__(kFoldThreads, kFoldWgsPerCu) void antt_fold(FoldPar
 	constexpr int kSlots = kFoldTile / 2 / kFoldThreads;  // level-0 pairs per thread
 	const int tid = threadIdx.x;
 
-	// ---- the tables of r_0 .. r_{arity-1}: the unit elements' products (entries 1, 2, 4, 8 of every
-	// nibble position; four levels at a time, 128 threads each), then the other entries by linearity
+	// ---- the tables of r_0 .. r_{arity-1} (four levels at a time)
 	gf8_tables_to_lds(tab);
 	__syncthreads();
-	for (int l0 = 0; l0 < P.arity; l0 += kFoldThreads / 128) {
-		const int l = __builtin_amdgcn_readfirstlane(l0 + (tid >> 7));
-		if (l < P.arity) {
-			const int j = tid & 127;  // the unit element 1 << j
-			const uint32_t bit = 1u << (j & 31);
-			const uint4 e = make_uint4((j >> 5) == 0 ? bit : 0u, (j >> 5) == 1 ? bit : 0u, (j >> 5) == 2 ? bit : 0u,
-			                           (j >> 5) == 3 ? bit : 0u);
-			rtab[l * kFoldRTab + (j >> 2) * 16 + (1 << (j & 3))] = dmul128_t(e, P.r[l], tab);
-		}
-	}
-	__syncthreads();
-	for (int i = tid; i < P.arity * kFoldRTab; i += kFoldThreads) {
-		const int e = i & 15;
-		if ((e & (e - 1)) != 0 || e == 0) {  // not a unit entry: those are only read here
-			const uint4* units = rtab + (i & ~15);
-			uint4 acc = make_uint4(0, 0, 0, 0);
-#pragma unroll
-			for (int b = 0; b < 4; b++)
-				if ((e >> b) & 1) acc = xor4(acc, units[1 << b]);
-			rtab[i] = acc;
-		}
-	}
-	__syncthreads();
+	fold_build_rtab<kFoldThreads>(rtab, P.arity, [&](int l, int j) {
+		const uint32_t bit = 1u << (j & 31);
+		const uint4 e = make_uint4((j >> 5) == 0 ? bit : 0u, (j >> 5) == 1 ? bit : 0u, (j >> 5) == 2 ? bit : 0u,
+		                           (j >> 5) == 3 ? bit : 0u);
+		return dmul128_t(e, P.r[l], tab);
+	});
 
 	const unsigned long long n_tiles = (P.n_in + kFoldTile - 1) >> kFoldTileLog;
 	for (unsigned long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {

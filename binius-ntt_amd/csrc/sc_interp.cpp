@@ -97,3 +97,23 @@ extern "C" int bn_sumcheck_interpolate(const uint32_t* points, int num_points, c
 	out[3] = (uint32_t)(acc.hi >> 32);
 	return BN_OK;
 }
+
+// bn_eq_eval: eq(a, b) = prod_i (a_i b_i ^ (1 ^ a_i)(1 ^ b_i)) (host only). In characteristic 2 the
+// factor is 1 ^ a_i ^ b_i, so a variable costs the one product that accumulates it.
+extern "C" int bn_eq_eval(int num_vars, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+	BN_CHECK_ARG(num_vars >= 0 && num_vars <= 128, "num_vars must be in [0, 128] (got %d)", num_vars);
+	BN_CHECK_ARG(out != nullptr && ((a != nullptr && b != nullptr) || num_vars == 0), "NULL argument");
+	auto ld = [](const uint32_t* p) { return bn::u128p{(uint64_t)p[0] | ((uint64_t)p[1] << 32), (uint64_t)p[2] | ((uint64_t)p[3] << 32)}; };
+	bn::u128p acc{1, 0};
+	for (int i = 0; i < num_vars; i++) {
+		const bn::u128p x = ld(a + 4 * i), y = ld(b + 4 * i);
+		// a b ^ (1 ^ a)(1 ^ b) = 1 ^ a ^ b (the two a b cancel)
+		const bn::u128p f{1 ^ x.lo ^ y.lo, x.hi ^ y.hi};
+		acc = bn::tw_mul128_host(acc, f);
+	}
+	out[0] = (uint32_t)acc.lo;
+	out[1] = (uint32_t)(acc.lo >> 32);
+	out[2] = (uint32_t)acc.hi;
+	out[3] = (uint32_t)(acc.hi >> 32);
+	return BN_OK;
+}

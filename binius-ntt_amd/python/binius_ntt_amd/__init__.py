@@ -105,6 +105,11 @@ def lib():
         "bn_multilinear_composition_eval": (i32, [i32, i32, i32, i32, u32p, u32p, u32p]),
         "bn_multilinear_composition_eval_device": (i32, [i32, i32, i32, i32, vp, u32p, u32p]),
         "bn_sumcheck_interpolate": (i32, [u32p, i32, u32p, u32p]),
+        "bn_eq_expand_device": (i32, [i32, u32p, u32p, vp, i32, vp]),
+        "bn_eq_expand_host": (i32, [i32, i32, u32p, u32p, i32, u32p]),
+        "bn_eq_eval": (i32, [i32, u32p, u32p, u32p]),
+        "bn_eq_expand_device_split": (i32, [i32, u32p, u32p, vp, i32, i32, vp]),
+        "bn_eq_expand_passes": (i32, [i32, i32, ctypes.POINTER(ctypes.c_int32), sz, ctypes.POINTER(i32)]),
         "bn_bb31_ntt_plan_create": (i32, [i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(vp)]),
         "bn_bb31_ntt_plan_destroy": (i32, [vp]),
         "bn_bb31_ntt_forward_host": (i32, [vp, vp, sz, vp, i32]),
@@ -756,3 +761,58 @@ def evaluate_univariate_given_points(challenge, points):
     out = np.zeros(4, np.uint32)
     _check(lib().bn_sumcheck_interpolate(_u32p(p), p.size // 4, _u32p(c), _u32p(out)))
     return out
+
+
+# ------------------------------------------------------------------ eq-indicator expansion
+def _eq_args(num_vars, challenges, scale):
+    """The (num_vars, 4) challenges and the 4-word scale (or None) as arrays and C pointers."""
+    ch = np.ascontiguousarray(challenges, dtype=np.uint32)
+    if ch.size == 0:
+        ch = ch.reshape(0, 4)
+    if ch.shape != (num_vars, 4):
+        raise ValueError("challenges must be a (num_vars, 4) uint32 array")
+    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.uint32).reshape(4)
+    return ch, sc, (_u32p(ch) if num_vars > 0 else None), (None if sc is None else _u32p(sc))
+
+
+def eq_expand(num_vars, challenges, out, scale=None, bitsliced=False, stream=None, max_levels=0):
+    """bn_eq_expand_device: E[x] = scale * prod_i (bit_{n-1-i}(x) ? r_i : 1 ^ r_i) into the device
+    tensor `out` (4 * 2^num_vars words), compact or bitsliced; `challenges` is a (num_vars, 4) uint32
+    host array, highest variable first. Async on `stream` (default: torch's current stream of out's
+    device). max_levels != 0 forces the per-pass level cap (bn_eq_expand_device_split, a test hook)."""
+    ch, sc, chp, scp = _eq_args(num_vars, challenges, scale)
+    if 0 <= num_vars <= 30:  # else: the library's own error
+        _check_device_tensor(out, 4 << num_vars, "out")
+    st = _stream(stream, _dev_index(out))
+    if max_levels:
+        _check(lib().bn_eq_expand_device_split(num_vars, chp, scp, _ptr(out), 1 if bitsliced else 0, max_levels, st))
+    else:
+        _check(lib().bn_eq_expand_device(num_vars, chp, scp, _ptr(out), 1 if bitsliced else 0, st))
+
+
+def eq_expand_host(num_vars, challenges, scale=None, bitsliced=False, device=0):
+    """bn_eq_expand_host: the same into a new (2^num_vars, 4) uint32 host array (bitsliced: the
+    blocks' words in that shape), synchronous."""
+    ch, sc, chp, scp = _eq_args(num_vars, challenges, scale)
+    out = np.zeros((1 << num_vars if 0 <= num_vars <= 30 else 1, 4), np.uint32)
+    _check(lib().bn_eq_expand_host(device, num_vars, chp, scp, 1 if bitsliced else 0, _u32p(out)))
+    return out
+
+
+def eq_eval(a, b):
+    """bn_eq_eval: prod_i (a_i b_i ^ (1 ^ a_i)(1 ^ b_i)) for two (n, 4) uint32 points (host arithmetic)."""
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 4)
+    b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1, 4)
+    if a.shape != b.shape:
+        raise ValueError("the points differ in length")
+    out = np.zeros(4, np.uint32)
+    _check(lib().bn_eq_eval(a.shape[0], _u32p(a), _u32p(b), _u32p(out)))
+    return out
+
+
+def eq_expand_passes(num_vars, max_levels=0):
+    """bn_eq_expand_passes: the levels of each pass of the expansion, first pass first (host only)."""
+    levels = (ctypes.c_int32 * 32)()
+    n = ctypes.c_int()
+    _check(lib().bn_eq_expand_passes(num_vars, max_levels, levels, 32, ctypes.byref(n)))
+    return [levels[i] for i in range(n.value)]

@@ -331,6 +331,51 @@ int bn_multilinear_composition_eval_device(int device, int num_vars, int composi
  * at `challenge`. Host arithmetic; 1 <= num_points <= 16. */
 int bn_sumcheck_interpolate(const uint32_t* points, int num_points, const uint32_t* challenge, uint32_t* out);
 
+/* ------------------------------------------------------------------------------------
+ * The eq-indicator (tensor) expansion of a point (no reference counterpart): the column that
+ * turns a sumcheck into a zerocheck or an evaluation claim
+ * ------------------------------------------------------------------------------------ */
+/* Writes E[x] = scale * prod_{i<n} ( bit_{n-1-i}(x) ? r_i : 1 ^ r_i ), x = 0 .. 2^n - 1, n = num_vars,
+ * to device memory, bit-exact. The convention is bn_multilinear_composition_eval's: `challenges` is
+ * num_vars x 4 words of host memory, r_i = challenges[i], highest variable first (challenges[i] pairs
+ * with index bit n-1-i), so that for scale = 1
+ *   XOR_x f[x]*E[x] == bn_multilinear_composition_eval(f, n, 1, challenges).
+ * d_out receives 2^n elements: compact (16 bytes each) when bitsliced == 0, else bitsliced 128-word
+ * blocks in element order, the layout of bn_bitslice_device and of a data_is_transposed sumcheck
+ * column (the buffer can be handed to bn_sumcheck_create_device as a column as it is). `scale` is 4
+ * words of host memory, or NULL for 1 (a shard driver passes the table over the variables it does
+ * not hold). `challenges` and `scale` are read before the call returns (passed to the kernels by
+ * value: no staging copy and no synchronisation, the call is asynchronous on `stream`). One level
+ * takes the table A over the k highest variables to k + 1 (hi = A[y]*r_k, lo = A[y] ^ hi): 2^n - 1
+ * products in all, each by a launch constant. The levels run in place in d_out in passes of at
+ * most 12 (30 = 6 + 12 + 12) and the call allocates nothing; d_out's contents between the passes are
+ * partial tables. Bitsliced output runs the in-place bit transpose behind the last pass. Runs on
+ * the current device, as bn_gf128_mul_device does.
+ * 0 <= num_vars <= 30, and >= 5 when bitsliced; all indexing is 64-bit. BN_ERR_INVALID, with nothing
+ * launched: num_vars out of range, a NULL d_out, NULL challenges with num_vars > 0, bitsliced with
+ * num_vars < 5. */
+int bn_eq_expand_device(int num_vars, const uint32_t* challenges, const uint32_t* scale, void* d_out, int bitsliced,
+                        void* stream);
+/* The same into host memory (2^num_vars x 4 words), synchronous, staged through a buffer on
+ * `device` that lives for the call. */
+int bn_eq_expand_host(int device, int num_vars, const uint32_t* challenges, const uint32_t* scale, int bitsliced,
+                      uint32_t* out);
+/* out = prod_{i<num_vars} (a_i*b_i ^ (1 ^ a_i)*(1 ^ b_i)): the value of the expansion of a at the
+ * point b (symmetric; the order of the variables does not matter as long as a and b agree), which a
+ * verifier needs for a zerocheck's last claim. a, b: num_vars x 4 words. Host arithmetic;
+ * 0 <= num_vars <= 128. */
+int bn_eq_eval(int num_vars, const uint32_t* a, const uint32_t* b, uint32_t* out);
+/* Test hook: bn_eq_expand_device with the per-pass level cap forced to max_levels, 3 .. 12 (0: the
+ * default, 12; other values BN_ERR_INVALID), so that three- and four-pass plans run at 2^9 - 2^13
+ * elements. Results are identical. */
+int bn_eq_expand_device_split(int num_vars, const uint32_t* challenges, const uint32_t* scale, void* d_out,
+                              int bitsliced, int max_levels, void* stream);
+/* Test hook (host only: no device): the host planner's split of num_vars levels at the cap
+ * max_levels (as above), levels[p] of pass p, first pass first; *n_passes passes (none for
+ * num_vars == 0). The last pass has min(num_vars, cap) levels, the passes before it cap each and the
+ * first the remainder. BN_ERR_INVALID if an argument is out of range or cap < *n_passes. */
+int bn_eq_expand_passes(int num_vars, int max_levels, int32_t* levels, size_t cap, int* n_passes);
+
 
 /* ------------------------------------------------------------------------------------
  * BabyBear radix-2 NTT, the prime-field sibling path (src/ulvt/ntt/gpuntt.cuh,

@@ -27,6 +27,10 @@ fold (only with --only fold) FRI-Binius fold of a 2^24-element GF(2^128) codewor
     bn_gf128_mul_device on 2^23 products (the arity-1 round's traffic and full-product count) in the
     same process; ms per call, the two ratios DESIGN.md section 5.8 states bounds for, and the
     fractions of HBM peak.
+eq  (only with --only eq) eq-indicator expansion of n GF(2^128) challenges, n = 24 (compact, and
+    bitsliced next to compact + bn_bitslice_device in alternating pairs) and n = 20, with
+    bn_gf128_mul_device on 2^n products first and last in the same process (the yardstick DESIGN.md
+    section 6.1 states the bound for) and a plain device fill of the same bytes (the write floor).
 Every line is one JSON object.
 """
 import argparse
@@ -201,6 +205,44 @@ def fold_line(dev, out, log_h=22, log_rate=2, reps=30):
          "hbm_peak_fraction_arity1": peak([1], ms_a1), "hbm_peak_fraction_arity4": peak([4], ms_a4),
          "hbm_peak_fraction_full_schedule": peak(full, ms_full),
          "hbm_peak_fraction_gf128_mul": 24.0 * n / (mul * 1e-3) / HBM_PEAK, "hbm_peak_bytes_per_s": HBM_PEAK})
+
+
+def eq_line(dev, out, n, bitsliced_too, reps=30):
+    """The eq-indicator expansion at 2^n elements: the compact call (and, if asked, the bitsliced call
+    next to the compact call followed by bn_bitslice_device), with bn_gf128_mul_device on 2^n products
+    timed first and last as the yardstick (the smaller reading counts) and a plain device fill of the
+    same 2^n x 16 B as the write floor, all in one process; ms per call, device events after a
+    warm-up call."""
+    import torch
+    import binius_ntt_amd as B
+    g = np.random.default_rng(11)
+    st = torch.cuda.current_stream(dev)
+    ch = g.integers(0, 2**32, size=(n, 4), dtype=np.uint64).astype(np.uint32)
+    e = torch.empty(4 << n, dtype=torch.int32, device=dev)
+    a = torch.randint(-2**31, 2**31, (4 << n,), dtype=torch.int32, device=dev)
+    b = torch.randint(-2**31, 2**31, (4 << n,), dtype=torch.int32, device=dev)
+
+    def then_bitslice():
+        B.eq_expand(n, ch, e, stream=st)
+        B.bitslice(e, stream=st)
+
+    ms_mul = [ev_time(lambda: B.gf128_mul(a, b, e, stream=st), reps, st)]
+    ms_fill = ev_time(lambda: e.fill_(0x5A5A5A5A), reps, st)
+    ms_eq = ev_time(lambda: B.eq_expand(n, ch, e, stream=st), reps, st)
+    line = {"config": "eq", "workload": "eq-indicator expansion of %d GF(2^128) challenges (2^%d elements)" % (n, n),
+            "kernel": "bn::eq_expand_pass", "passes": B.eq_expand_passes(n), "value": (1 << n) / (ms_eq * 1e-3),
+            "unit": "elements/s", "ms": ms_eq, "ms_fill": ms_fill}
+    if bitsliced_too:
+        # alternating pairs: the library's bitsliced call against the compact call plus bn_bitslice_device
+        pairs = [(ev_time(lambda: B.eq_expand(n, ch, e, bitsliced=True, stream=st), reps, st), ev_time(then_bitslice, reps, st))
+                 for _ in range(3)]
+        line["ms_bitsliced_vs_compact_then_bitslice"] = pairs
+    ms_mul.append(ev_time(lambda: B.gf128_mul(a, b, e, stream=st), reps, st))
+    mul = min(ms_mul)
+    line.update({"ms_gf128_mul_2p%d" % n: ms_mul, "over_gf128_mul": ms_eq / mul, "bound_over_gf128_mul": 1.0,
+                 "over_fill": ms_eq / ms_fill, "hbm_peak_fraction": (16 << n) / (ms_eq * 1e-3) / HBM_PEAK,
+                 "hbm_peak_bytes_per_s": HBM_PEAK})
+    out(line)
 
 
 def c4(dev, out, nvars, ds):
@@ -411,6 +453,9 @@ def main():
         intt_line(dev, out, 24)
     if "fold" in only:
         fold_line(dev, out)
+    if "eq" in only:
+        eq_line(dev, out, 24, True)
+        eq_line(dev, out, 20, False)
     if a.out:
         with open(a.out, "w") as f:
             for d in lines:
