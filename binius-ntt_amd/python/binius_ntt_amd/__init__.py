@@ -110,6 +110,17 @@ def lib():
         "bn_eq_eval": (i32, [i32, u32p, u32p, u32p]),
         "bn_eq_expand_device_split": (i32, [i32, u32p, u32p, vp, i32, i32, vp]),
         "bn_eq_expand_passes": (i32, [i32, i32, ctypes.POINTER(ctypes.c_int32), sz, ctypes.POINTER(i32)]),
+        "bn_merkle_tree_digests": (i32, [i32, ctypes.POINTER(sz)]),
+        "bn_merkle_open_bytes": (i32, [i32, i32, ctypes.POINTER(sz)]),
+        "bn_merkle_row_offset": (i32, [i32, i32, ctypes.POINTER(sz)]),
+        "bn_merkle_commit_device": (i32, [vp, i32, i32, vp, vp]),
+        "bn_merkle_commit_device_split": (i32, [vp, i32, i32, vp, i32, vp]),
+        "bn_merkle_commit_host": (i32, [i32, vp, i32, i32, vp]),
+        "bn_merkle_open_device": (i32, [vp, vp, i32, i32, vp, sz, vp, vp]),
+        "bn_merkle_hash_leaf": (i32, [vp, i32, vp]),
+        "bn_merkle_hash_node": (i32, [vp, vp, vp]),
+        "bn_merkle_verify": (i32, [vp, i32, i32, ctypes.c_uint64, vp, ctypes.POINTER(i32)]),
+        "bn_merkle_commit_passes": (i32, [i32, i32, i32, ctypes.POINTER(ctypes.c_int32), sz, ctypes.POINTER(i32)]),
         "bn_bb31_ntt_plan_create": (i32, [i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(vp)]),
         "bn_bb31_ntt_plan_destroy": (i32, [vp]),
         "bn_bb31_ntt_forward_host": (i32, [vp, vp, sz, vp, i32]),
@@ -816,3 +827,126 @@ def eq_expand_passes(num_vars, max_levels=0):
     n = ctypes.c_int()
     _check(lib().bn_eq_expand_passes(num_vars, max_levels, levels, 32, ctypes.byref(n)))
     return [levels[i] for i in range(n.value)]
+
+
+# ------------------------------------------------------------------ SHA-256 Merkle commitment
+MERKLE_LEAF, MERKLE_ROW, MERKLE_TAIL = 0, 1, 2
+
+
+def _merkle_size(fn, *args):
+    n = ctypes.c_size_t()
+    _check(fn(*args, ctypes.byref(n)))
+    return n.value
+
+
+def merkle_tree_digests(log_leaves):
+    """bn_merkle_tree_digests: 2^(L+1) - 1, the 32-byte digests of the tree buffer."""
+    return _merkle_size(lib().bn_merkle_tree_digests, log_leaves)
+
+
+def merkle_row_offset(log_leaves, row):
+    """bn_merkle_row_offset: the digest index of node 0 of `row` (row 0: the leaf digests; row L: the root)."""
+    return _merkle_size(lib().bn_merkle_row_offset, log_leaves, row)
+
+
+def merkle_open_bytes(log_leaves, log_leaf_elems):
+    """bn_merkle_open_bytes: the bytes of one opening record, 16 * 2^a + 32 * L."""
+    return _merkle_size(lib().bn_merkle_open_bytes, log_leaves, log_leaf_elems)
+
+
+def _merkle_shape_ok(log_leaves, log_leaf_elems):
+    return 0 <= log_leaf_elems <= 8 and 0 <= log_leaves and log_leaves + log_leaf_elems <= 30
+
+
+def merkle_commit(data, log_leaves, log_leaf_elems, tree, stream=None, max_rows=0):
+    """bn_merkle_commit_device: the SHA-256 Merkle tree of the 2^(L+a) compact elements in the device
+    tensor `data` (leaf j: elements [j << a, (j + 1) << a)) into the device tensor `tree`
+    (32 * (2^(L+1) - 1) bytes, row 0 first, the root last). Async on `stream` (default: torch's current
+    stream of data's device); `data` is not written. max_rows != 0 forces the planner's rows-per-pass
+    cap (bn_merkle_commit_device_split, a test hook)."""
+    if _merkle_shape_ok(log_leaves, log_leaf_elems):  # else: the library's own error
+        _check_device_tensor(data, 4 << (log_leaves + log_leaf_elems), "data")
+        _check_device_tensor(tree, 8 * merkle_tree_digests(log_leaves), "tree")
+    st = _stream(stream, _dev_index(data))
+    if max_rows:
+        _check(lib().bn_merkle_commit_device_split(_ptr(data), log_leaves, log_leaf_elems, _ptr(tree), max_rows, st))
+    else:
+        _check(lib().bn_merkle_commit_device(_ptr(data), log_leaves, log_leaf_elems, _ptr(tree), st))
+
+
+def merkle_commit_host(data, log_leaf_elems, device=0):
+    """bn_merkle_commit_host: the tree of a host array of 2^(L+a) elements ((n, 4) uint32), as a new
+    (2^(L+1) - 1, 32) uint8 array; synchronous. L is taken from the array's size."""
+    d = np.ascontiguousarray(data, dtype=np.uint32).reshape(-1, 4)
+    n = d.shape[0]
+    if n == 0 or n & (n - 1) or not 0 <= log_leaf_elems <= 8 or n >> log_leaf_elems == 0:
+        raise ValueError("data must hold a power of two of elements, at least one leaf")
+    log_leaves = n.bit_length() - 1 - log_leaf_elems
+    tree = np.zeros(((2 << log_leaves) - 1, 32), np.uint8)
+    _check(lib().bn_merkle_commit_host(device, d.ctypes.data, log_leaves, log_leaf_elems, tree.ctypes.data))
+    return tree
+
+
+def merkle_open(data, tree, log_leaves, log_leaf_elems, indices, out, stream=None):
+    """bn_merkle_open_device: the opening record of leaf indices[q] (the leaf's bytes, then the L
+    sibling digests from the bottom up) at out + q * merkle_open_bytes(L, a). `indices` is a device
+    tensor of 32-bit integers; an index >= 2^L gives an all-zero record. Async on `stream`."""
+    nq = 0 if isinstance(indices, int) else indices.numel()
+    if not isinstance(indices, int) and indices.element_size() != 4:
+        raise ValueError("indices must be a tensor of 32-bit integers")
+    if _merkle_shape_ok(log_leaves, log_leaf_elems):  # else: the library's own error
+        _check_device_tensor(data, 4 << (log_leaves + log_leaf_elems), "data")
+        _check_device_tensor(tree, 8 * merkle_tree_digests(log_leaves), "tree")
+        _check_device_tensor(indices, nq, "indices")
+        _check_device_tensor(out, nq * merkle_open_bytes(log_leaves, log_leaf_elems) // 4, "out")
+    _check(lib().bn_merkle_open_device(_ptr(data), _ptr(tree), log_leaves, log_leaf_elems, _ptr(indices), nq, _ptr(out),
+                                       _stream(stream, _dev_index(data))))
+
+
+def _bytes32(b, what):
+    a = np.frombuffer(bytes(b), dtype=np.uint8) if isinstance(b, (bytes, bytearray)) else np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+    if a.size != 32:
+        raise ValueError("%s must be 32 bytes" % what)
+    return np.ascontiguousarray(a)
+
+
+def merkle_hash_leaf(leaf, log_leaf_elems):
+    """bn_merkle_hash_leaf: the digest (32 bytes) of a leaf of 16 << a bytes (host arithmetic)."""
+    a = np.frombuffer(bytes(leaf), dtype=np.uint8) if isinstance(leaf, (bytes, bytearray)) else np.ascontiguousarray(leaf).view(np.uint8).reshape(-1)
+    if 0 <= log_leaf_elems <= 8 and a.size != 16 << log_leaf_elems:
+        raise ValueError("the leaf holds %d bytes, need %d" % (a.size, 16 << log_leaf_elems))
+    a = np.ascontiguousarray(a)
+    out = np.zeros(32, np.uint8)
+    _check(lib().bn_merkle_hash_leaf(a.ctypes.data, log_leaf_elems, out.ctypes.data))
+    return out.tobytes()
+
+
+def merkle_hash_node(left, right):
+    """bn_merkle_hash_node: one compression of left || right from the initial state (host arithmetic)."""
+    l, r = _bytes32(left, "left"), _bytes32(right, "right")
+    out = np.zeros(32, np.uint8)
+    _check(lib().bn_merkle_hash_node(l.ctypes.data, r.ctypes.data, out.ctypes.data))
+    return out.tobytes()
+
+
+def merkle_verify(root, log_leaves, log_leaf_elems, index, record):
+    """bn_merkle_verify: True if the opening record of leaf `index` hashes to `root` (host arithmetic)."""
+    rt = _bytes32(root, "root")
+    rec = np.frombuffer(bytes(record), dtype=np.uint8) if isinstance(record, (bytes, bytearray)) else np.ascontiguousarray(record).view(np.uint8).reshape(-1)
+    if _merkle_shape_ok(log_leaves, log_leaf_elems) and rec.size != merkle_open_bytes(log_leaves, log_leaf_elems):
+        raise ValueError("the record holds %d bytes, need %d" % (rec.size, merkle_open_bytes(log_leaves, log_leaf_elems)))
+    if index < 0:
+        return False
+    rec = np.ascontiguousarray(rec)
+    ok = ctypes.c_int()
+    _check(lib().bn_merkle_verify(rt.ctypes.data, log_leaves, log_leaf_elems, index, rec.ctypes.data, ctypes.byref(ok)))
+    return bool(ok.value)
+
+
+def merkle_commit_passes(log_leaves, log_leaf_elems, max_rows=0):
+    """bn_merkle_commit_passes: the planner's passes as (kind, first row written, rows written), kind
+    MERKLE_LEAF, MERKLE_ROW or MERKLE_TAIL (host only)."""
+    out = (ctypes.c_int32 * 96)()
+    n = ctypes.c_int()
+    _check(lib().bn_merkle_commit_passes(log_leaves, log_leaf_elems, max_rows, out, 32, ctypes.byref(n)))
+    return [(out[3 * i], out[3 * i + 1], out[3 * i + 2]) for i in range(n.value)]

@@ -376,6 +376,75 @@ int bn_eq_expand_device_split(int num_vars, const uint32_t* challenges, const ui
  * first the remainder. BN_ERR_INVALID if an argument is out of range or cap < *n_passes. */
 int bn_eq_expand_passes(int num_vars, int max_levels, int32_t* levels, size_t cap, int* n_passes);
 
+/* ------------------------------------------------------------------------------------
+ * SHA-256 Merkle commitment of a device-resident GF(2^128) codeword and its query openings (no
+ * reference counterpart): the step between bn_antt_forward_device and bn_antt_fri_fold_device, and
+ * between one fold and the next. Every result is bit-exact.
+ *
+ * The rule. L = log_leaves, a = log_leaf_elems (0 .. 8), L + a <= 30.
+ *   Input        2^L leaves. Leaf j is the 2^a consecutive compact elements [j << a, (j + 1) << a) of one
+ *                flat buffer: the elements one bn_antt_fri_fold_device call of arity a folds into
+ *                output element j (round + arity <= log_h there, so a leaf never straddles a coset
+ *                block).
+ *   Leaf digest  SHA-256 (FIPS 180-4, with its padding) of the leaf's 16 << a bytes as they lie in
+ *                memory (four little-endian uint32 limbs per element, limb 0 first).
+ *   Node digest  one SHA-256 compression, no padding and no length block: the state starts at the
+ *                standard initial value, the 64-byte block is left || right, the digest is the eight
+ *                state words after the feed-forward addition, each big-endian. Two all-zero children
+ *                give da5698be17b9b46962335799779fbeca8ce5d491c0d26243bafef9ea1837a9d8. With L = 0 the
+ *                root is the leaf digest.
+ *   Tree buffer  2^(L+1) - 1 digests of 32 bytes. Row 0 (the 2^L leaf digests) first, then row 1
+ *                (2^(L-1) nodes), ..., the root last at digest index 2^(L+1) - 2. Row h starts at digest
+ *                index 2^(L+1) - 2^(L-h+1); node k of row h + 1 is node(row_h[2k], row_h[2k+1]).
+ *   Opening      of leaf j: the leaf's 16 << a bytes, then L sibling digests from the bottom up, the
+ *                one at row h being row_h[(j >> h) ^ 1]: 16 * 2^a + 32 * L bytes.
+ * All element and byte offsets are 64-bit. Device buffers must be 16-byte aligned.
+ * ------------------------------------------------------------------------------------ */
+/* The two sizes (host only): *n = 2^(L+1) - 1 digests of the tree buffer (0 <= L <= 30); *bytes of one
+ * opening record. */
+int bn_merkle_tree_digests(int log_leaves, size_t* n);
+int bn_merkle_open_bytes(int log_leaves, int log_leaf_elems, size_t* bytes);
+/* *index = the digest index of node 0 of `row` (0 <= row <= log_leaves) in the tree buffer (host only). */
+int bn_merkle_row_offset(int log_leaves, int row, size_t* index);
+/* Commits to the 2^(L+a) elements at d_data: fills d_tree (32 * (2^(L+1) - 1) bytes) by the rule
+ * above. Asynchronous on `stream`; allocates nothing and uses no scratch buffer: the rows are written
+ * into d_tree and read back from it by the later passes (a leaf pass of 256 leaves a work-group that
+ * goes on to rows 1 and 2, row passes of three rows each, and one work-group that finishes the tree
+ * from a row of at most 2^9 digests), stream order being the only synchronisation. d_data is not
+ * written. Runs on the current device.
+ * BN_ERR_INVALID, with nothing launched and no buffer touched: a NULL or misaligned pointer,
+ * log_leaf_elems outside [0, 8], log_leaves < 0 or log_leaves + log_leaf_elems > 30, overlapping
+ * d_data and d_tree ranges. */
+int bn_merkle_commit_device(const void* d_data, int log_leaves, int log_leaf_elems, void* d_tree, void* stream);
+/* Test hook: the same with the planner's rows-per-pass cap forced to max_rows, 1 .. 3, for every
+ * pass, the tail included (0: the default, three rows for the leaf and row passes and up to nine for
+ * the tail; other values BN_ERR_INVALID), so that a tree of 2^10 leaves has several row passes.
+ * Results are identical. */
+int bn_merkle_commit_device_split(const void* d_data, int log_leaves, int log_leaf_elems, void* d_tree, int max_rows,
+                                  void* stream);
+/* The same on host buffers (data: 2^(L+a) x 4 words, tree: 32 * (2^(L+1) - 1) bytes), synchronous,
+ * staged through a buffer on `device` that lives for the call. */
+int bn_merkle_commit_host(int device, const uint32_t* data, int log_leaves, int log_leaf_elems, uint8_t* tree);
+/* Writes the opening record of leaf d_indices[q] at d_out + q * record bytes, q = 0 .. n_queries - 1.
+ * d_indices is device memory (uint32), so the call needs no staging copy and is asynchronous on
+ * `stream`; queued behind the commitment on the same stream it needs no synchronisation. An index
+ * >= 2^L gives an all-zero record and reads nothing out of range; duplicates are allowed.
+ * BN_ERR_INVALID, with nothing launched: as for the commitment, n_queries == 0 (or above 2^40 bytes
+ * of records), d_out overlapping d_data, d_tree or d_indices. */
+int bn_merkle_open_device(const void* d_data, const void* d_tree, int log_leaves, int log_leaf_elems,
+                          const uint32_t* d_indices, size_t n_queries, void* d_out, void* stream);
+/* What a verifier needs (host integer code, no device): the digest of a leaf of 16 << log_leaf_elems
+ * bytes, the digest of a node, and the check of an opening record of leaf `index` against a root
+ * (*ok = 1 if the path hashes to root32, else 0, also for index >= 2^L). */
+int bn_merkle_hash_leaf(const void* leaf, int log_leaf_elems, uint8_t* out32);
+int bn_merkle_hash_node(const uint8_t* left32, const uint8_t* right32, uint8_t* out32);
+int bn_merkle_verify(const uint8_t* root32, int log_leaves, int log_leaf_elems, uint64_t index, const void* record, int* ok);
+/* Test hook (host only): the planner's split of the rows 0 .. L at the cap max_rows (as above). Pass
+ * p is out[3p .. 3p+2] = kind (0 leaf pass, 1 row pass, 2 tail), the first row it writes, the number
+ * of rows it writes; *n_passes passes, at most 32. One leaf pass first; the tail, if any, last.
+ * BN_ERR_INVALID if an argument is out of range or cap < *n_passes. */
+int bn_merkle_commit_passes(int log_leaves, int log_leaf_elems, int max_rows, int32_t* out, size_t cap, int* n_passes);
+
 
 /* ------------------------------------------------------------------------------------
  * BabyBear radix-2 NTT, the prime-field sibling path (src/ulvt/ntt/gpuntt.cuh,

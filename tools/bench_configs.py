@@ -31,6 +31,12 @@ eq  (only with --only eq) eq-indicator expansion of n GF(2^128) challenges, n = 
     bitsliced next to compact + bn_bitslice_device in alternating pairs) and n = 20, with
     bn_gf128_mul_device on 2^n products first and last in the same process (the yardstick DESIGN.md
     section 6.1 states the bound for) and a plain device fill of the same bytes (the write floor).
+merkle (only with --only merkle) SHA-256 Merkle commitment of the fold line's codeword (log_h 22,
+    log_rate 2, 2^24 elements): the commit at a = 1 and a = 4, bn_antt_forward_device on the same plan
+    (the encode that produces this codeword; the yardstick DESIGN.md section 5.9 states the bound
+    for), a device-to-device copy of the same 256 MiB, and the six commits of the 4+4+4+4+4+2
+    schedule next to its six folds, all in one process; ms, leaves/s, compressions/s, the share of
+    the HBM peak and the share of the v_bitop3 issue ceiling from the static VALU count per compression.
 Every line is one JSON object.
 """
 import argparse
@@ -245,6 +251,75 @@ def eq_line(dev, out, n, bitsliced_too, reps=30):
     out(line)
 
 
+BITOP3_CEILING = 8.36e11    # wave-instructions/s chip-wide
+SHA_VALU_PER_BLOCK = 1400   # static VALU count of one unrolled compression in the ISA
+SHA_VALU_PER_PAD_BLOCK = 1000  # the all-padding block of a leaf of a >= 2: rounds only
+
+
+def merkle_line(dev, out, log_h=22, log_rate=2, reps=30):
+    """SHA-256 Merkle commitment of a 2^(log_h+log_rate)-element GF(2^128) codeword: a = 1 and a = 4,
+    the encode of the same plan, a device copy of the same bytes, and the commits of the fold schedule
+    next to its folds, all in one process; ms per call, device events after a warm-up call."""
+    import torch
+    import binius_ntt_amd as B
+    log_n = log_h + log_rate
+    n = 1 << log_n
+    g = np.random.default_rng(13)
+    st = torch.cuda.current_stream(dev)
+    ntt = B.AdditiveNTT(B.AdditiveNTTConf(log_h, log_rate, B.FanPaarTowerField(7), device=dev.index or 0))
+    ch = g.integers(0, 2**32, size=(log_h, 4), dtype=np.uint64).astype(np.uint32)
+    msg = torch.randint(-2**31, 2**31, (4 << log_h,), dtype=torch.int32, device=dev)
+    cw = torch.empty(4 * n, dtype=torch.int32, device=dev)
+    other = torch.empty(4 * n, dtype=torch.int32, device=dev)
+    tree = torch.empty(32 * B.merkle_tree_digests(log_n - 1), dtype=torch.uint8, device=dev)
+
+    def blocks(log_elems, a):
+        """(leaves, compressions, VALU lane-instructions) of a commit of 2^log_elems elements at leaf size a."""
+        leaves = 1 << (log_elems - a)
+        data = leaves * max(1, (16 << a) // 64)
+        pad = leaves if a >= 2 else 0
+        nodes = leaves - 1
+        return leaves, data + pad + nodes, (data + nodes) * SHA_VALU_PER_BLOCK + pad * SHA_VALU_PER_PAD_BLOCK
+
+    def stats(log_elems, a, ms):
+        leaves, comp, valu = blocks(log_elems, a)
+        t = ms * 1e-3
+        return {"ms": ms, "leaves_per_s": leaves / t, "compressions_per_s": comp / t,
+                "hbm_peak_fraction": ((16 << log_elems) + 32 * (2 * leaves - 1)) / t / HBM_PEAK,
+                "bitop3_ceiling_fraction": valu / 64 / t / BITOP3_CEILING,
+                "passes": B.merkle_commit_passes(log_elems - a, a)}
+
+    ms_enc = [ev_time(lambda: ntt.forward_device(msg, cw, stream=st), reps, st)]
+    ms_copy = ev_time(lambda: other.copy_(cw), reps, st)
+    ms_a1 = ev_time(lambda: B.merkle_commit(cw, log_n - 1, 1, tree, stream=st), reps, st)
+    ms_a4 = ev_time(lambda: B.merkle_commit(cw, log_n - 4, 4, tree, stream=st), reps, st)
+    ms_enc.append(ev_time(lambda: ntt.forward_device(msg, cw, stream=st), reps, st))
+    enc = min(ms_enc)
+    # the schedule: commit i is of the codeword of round rnd at a = the arity of the fold that follows
+    full = [4] * (log_h // 4) + ([log_h % 4] if log_h % 4 else [])
+    bufs = [cw, other]
+    sched = []
+    rnd, src = 0, 0
+    for k in full:
+        le = log_n - rnd
+        ms_c = ev_time(lambda le=le, k=k, src=src: B.merkle_commit(bufs[src], le - k, k, tree, stream=st), reps, st)
+        ms_f = ev_time(lambda rnd=rnd, k=k, src=src: ntt.fri_fold_device(bufs[src], bufs[1 - src], rnd, ch[rnd:rnd + k], stream=st), reps, st)
+        sched.append(dict(stats(le, k, ms_c), round=rnd, arity=k, log_elems=le, ms_fold=ms_f))
+        rnd, src = rnd + k, 1 - src
+    a1, a4 = stats(log_n, 1, ms_a1), stats(log_n, 4, ms_a4)
+    # the bound (DESIGN.md section 5.9): the a = 4 commit takes no longer than the encode timed in this
+    # process. Measured on one MI355X: 0.307 ms against 0.636 ms, a ratio of 0.48.
+    binding = "VALU" if a4["bitop3_ceiling_fraction"] > a4["hbm_peak_fraction"] else "HBM"
+    out({"config": "merkle", "workload": "SHA-256 Merkle commitment of a 2^%d-element GF(2^128) codeword (log_h %d, log_rate %d)"
+         % (log_n, log_h, log_rate), "kernel": "bn::merkle_leaf_pass / bn::merkle_row_pass",
+         "value": a4["leaves_per_s"], "unit": "leaves/s (a = 4)", "commit_a1": a1, "commit_a4": a4,
+         "ms_encode": ms_enc, "ms_copy_d2d": ms_copy, "a4_over_encode": ms_a4 / enc, "bound_a4_over_encode": 1.0,
+         "a1_over_encode": ms_a1 / enc, "a4_over_copy": ms_a4 / ms_copy, "binding_resource_a4": binding,
+         "schedule": sched, "ms_schedule_commits": sum(x["ms"] for x in sched), "ms_schedule_folds": sum(x["ms_fold"] for x in sched),
+         "valu_per_compression": SHA_VALU_PER_BLOCK, "valu_per_padding_block": SHA_VALU_PER_PAD_BLOCK,
+         "bitop3_ceiling_wave_instructions_per_s": BITOP3_CEILING, "hbm_peak_bytes_per_s": HBM_PEAK})
+
+
 def c4(dev, out, nvars, ds):
     import torch
     import binius_ntt_amd as B
@@ -456,6 +531,8 @@ def main():
     if "eq" in only:
         eq_line(dev, out, 24, True)
         eq_line(dev, out, 20, False)
+    if "merkle" in only:
+        merkle_line(dev, out)
     if a.out:
         with open(a.out, "w") as f:
             for d in lines:
