@@ -206,6 +206,18 @@ static void dev_variant_override(bn_antt_plan* p) {
 #endif
 }
 
+// the device side of a new plan: the subspace table, and the pass tables where the fast path applies
+static int plan_to_device(bn_antt_plan* p) {
+	BN_DEVICE_SCOPE(p->device);
+	if (int rc = dev_alloc(&p->s_dev, std::max<size_t>(p->s_host.size(), 1) * sizeof(uint32_t))) return rc;
+	if (!p->s_host.empty()) BN_HIP(hipMemcpy(p->s_dev, p->s_host.data(), p->s_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+	if (bs_supports(p->log_h, p->log_rate)) {
+		if (int rc = bs_prepare(p)) return rc;
+		dev_variant_override(p);
+	}
+	return BN_OK;
+}
+
 }  // namespace bn
 
 using namespace bn;
@@ -230,23 +242,10 @@ extern "C" int bn_antt_plan_create(int device, int field_bits, int log_h, int lo
 	p->limbs = field_bits / 32;
 	p->width = log_h + log_rate - 1;
 	subspace_evals(log_h, log_rate, p->s_host);
-	DeviceScope ds(device);
-	hipError_t e = ds.err;
-	if (e == hipSuccess) e = hipMalloc(&p->s_dev, std::max<size_t>(p->s_host.size(), 1) * sizeof(uint32_t));
-	if (e == hipSuccess && !p->s_host.empty())
-		e = hipMemcpy(p->s_dev, p->s_host.data(), p->s_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-	if (e != hipSuccess) {
-		bn_antt_plan_destroy(p);
-		BN_FAIL(BN_ERR_HIP, "plan allocation failed: %s", hipGetErrorString(e));
-	}
 	p->variant = 0;
-	if (bs_supports(log_h, log_rate)) {
-		const int rc = bs_prepare(p);
-		if (rc != BN_OK) {
-			bn_antt_plan_destroy(p);
-			return rc;
-		}
-		dev_variant_override(p);
+	if (const int rc = plan_to_device(p)) {
+		bn_antt_plan_destroy(p);
+		return rc;
 	}
 	*out = p;
 	return BN_OK;
@@ -295,7 +294,7 @@ static size_t block_bytes(const bn_antt_plan* p, size_t batch) { return ((size_t
 
 extern "C" int bn_antt_forward_device(bn_antt_plan* p, const void* d_in, void* d_out, size_t batch, void* stream) {
 	if (int rc = check_device_args(p, d_in, d_out, batch)) return rc;
-	if (int rc = check_no_overlap(d_in, block_bytes(p, batch), d_out, block_bytes(p, batch) << p->log_rate)) return rc;
+	BN_CHECK_IO_DISJOINT(d_in, block_bytes(p, batch), d_out, block_bytes(p, batch) << p->log_rate);
 	BN_DEVICE_SCOPE(p->device);
 	return forward_device_impl(p, d_in, d_out, batch, (hipStream_t)stream);
 }
@@ -304,7 +303,7 @@ extern "C" int bn_antt_inverse_device(bn_antt_plan* p, const void* d_in, void* d
                                       void* stream) {
 	if (int rc = check_device_args(p, d_in, d_out, batch)) return rc;
 	BN_CHECK_ARG(coset >= 0 && coset < (1 << p->log_rate), "coset must be in [0, 2^%d) (got %d)", p->log_rate, coset);
-	if (int rc = check_no_overlap(d_in, block_bytes(p, batch), d_out, block_bytes(p, batch))) return rc;
+	BN_CHECK_IO_DISJOINT(d_in, block_bytes(p, batch), d_out, block_bytes(p, batch));
 	BN_DEVICE_SCOPE(p->device);
 	return inverse_device_impl(p, d_in, d_out, coset, batch, (hipStream_t)stream);
 }
@@ -315,21 +314,20 @@ static int check_host_args(const bn_antt_plan* p, const void* in, size_t in_elem
 	BN_CHECK_ARG(in_elems == ((size_t)1 << p->log_h), "input has %zu elements, plan expects 2^%d", in_elems, p->log_h);
 	return BN_OK;
 }
-// Host in -> host out, synchronous, one transform: through the plan's staging buffers (allocated on
-// first use: 2^log_h elements in, every coset block out, which holds the inverse's one block too) and
-// its own stream. `launch(d_in, d_out, stream)` runs the transform between the two copies.
+// Host in -> host out, synchronous, one transform: a staged call through the plan's staging buffers
+// (allocated on first use: 2^log_h elements in, every coset block out, which holds the inverse's one
+// block too) and its own stream. `launch(d_in, d_out, stream)` runs the transform between the copies.
 template <class Launch>
 static int host_transform(bn_antt_plan* p, const void* in, void* out, size_t out_bytes, Launch launch) {
 	BN_DEVICE_SCOPE(p->device);
 	const size_t in_bytes = block_bytes(p, 1);
-	if (!p->h_dev_in) BN_HIP(hipMalloc(&p->h_dev_in, in_bytes));
-	if (!p->h_dev_out) BN_HIP(hipMalloc(&p->h_dev_out, in_bytes << p->log_rate));
+	if (!p->h_dev_in)
+		if (int rc = dev_alloc(&p->h_dev_in, in_bytes)) return rc;
+	if (!p->h_dev_out)
+		if (int rc = dev_alloc(&p->h_dev_out, in_bytes << p->log_rate)) return rc;
 	if (!p->own_stream) BN_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
-	BN_HIP(hipMemcpyAsync(p->h_dev_in, in, in_bytes, hipMemcpyHostToDevice, p->own_stream));
-	if (int rc = launch(p->h_dev_in, p->h_dev_out, p->own_stream)) return rc;
-	BN_HIP(hipMemcpyAsync(out, p->h_dev_out, out_bytes, hipMemcpyDeviceToHost, p->own_stream));
-	BN_HIP(hipStreamSynchronize(p->own_stream));
-	return BN_OK;
+	return staged_call(p->own_stream, in, p->h_dev_in, in_bytes, p->h_dev_out, out, out_bytes,
+	                   [&](hipStream_t st) { return launch(p->h_dev_in, p->h_dev_out, st); });
 }
 
 // AdditiveNTT::apply (additive_ntt.cuh:201-265)

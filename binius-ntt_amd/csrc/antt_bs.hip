@@ -708,7 +708,8 @@ static int launch_one(bn_antt_plan* plan, int i, const uint32_t* d_in, uint32_t*
 		constexpr size_t kTraceBytes = (size_t)1 << 26;
 		static unsigned long long* trbuf = nullptr;
 		if (waves * 8 * sizeof(*trbuf) > kTraceBytes) BN_FAIL(BN_ERR_UNSUPPORTED, "BN_TRACE: %zu waves do not fit the trace buffer", waves);
-		if (!trbuf) BN_HIP(hipMalloc(&trbuf, kTraceBytes));
+		if (!trbuf)
+			if (int rc = dev_alloc(&trbuf, kTraceBytes)) return rc;
 		BN_HIP(hipMemsetAsync(trbuf, 0, waves * 8 * sizeof(*trbuf), st));
 		prm.trace = trbuf;
 	}

@@ -11,23 +11,9 @@
 #include "antt_bs.hpp"
 #include "bitsliced.hpp"
 #include "bitsliced_ntt_gen.hpp"
+#include "stream_io.hpp"  // ld_stream / st_stream: every byte is touched once per pass
 
 namespace bn {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-// streaming (non-temporal) 16-byte global accesses: every byte is touched once per pass
-__device__ __forceinline__ uint4 ld_stream(const uint32_t* p) {
-	const u32x4 v = __builtin_nontemporal_load((const u32x4*)p);
-	return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st_stream(uint32_t* p, uint4 g) {
-	u32x4 v;
-	v.x = g.x;
-	v.y = g.y;
-	v.z = g.z;
-	v.w = g.w;
-	__builtin_nontemporal_store(v, (u32x4*)p);
-}
 
 // out = w*x for 32 bitsliced GF(2^32) limbs (alias-safe: out may be x). W holds bit i of each
 // lane's twiddle in word i; `field` (uniform per stage) selects the sub-field circuit, FMAX (the

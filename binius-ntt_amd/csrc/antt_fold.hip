@@ -179,9 +179,7 @@ int launch_fold(bn_antt_plan* plan, const void* d_in, void* d_out, int round, in
 	prm.round = round;
 	prm.arity = arity;
 	prm.n_in = (unsigned long long)batch << (plan->log_h + plan->log_rate - round);
-	for (int i = 0; i < kFoldMaxArity; i++)
-		prm.r[i] = i < arity ? make_uint4(challenges[4 * i], challenges[4 * i + 1], challenges[4 * i + 2], challenges[4 * i + 3])
-		                     : make_uint4(0, 0, 0, 0);
+	for (int i = 0; i < kFoldMaxArity; i++) prm.r[i] = i < arity ? words4(challenges + 4 * i) : make_uint4(0, 0, 0, 0);
 	// a tile holds whole chunks (2^arity <= kFoldTile) and the last one may be partly empty. One
 	// work-group per tile up to what the device holds at once; beyond that the work-groups stride,
 	// so the tables of r are built once per resident work-group (num_cus is known for log_h >= 12
@@ -220,7 +218,7 @@ extern "C" int bn_antt_fri_fold_device(bn_antt_plan* p, const void* d_in, void* 
 	const int log_in = p->log_h + p->log_rate - round;
 	BN_CHECK_ARG(batch <= (((size_t)1 << 40) >> log_in), "batch of %zu codewords is too large", batch);
 	const size_t in_bytes = (batch << log_in) * 16;
-	if (int rc = check_no_overlap(d_in, in_bytes, d_out, in_bytes >> arity)) return rc;
+	BN_CHECK_IO_DISJOINT(d_in, in_bytes, d_out, in_bytes >> arity);
 	BN_DEVICE_SCOPE(p->device);
 	return launch_fold(p, d_in, d_out, round, arity, challenges, batch, (hipStream_t)stream);
 }
@@ -237,17 +235,9 @@ extern "C" int bn_antt_fri_fold_host(bn_antt_plan* p, const void* in, size_t in_
 	const size_t out_bytes = in_bytes >> arity;
 	if (!p->own_stream) BN_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
 	// staged per call, input and output in one allocation: a fold's sizes depend on the round
-	void* d_src = nullptr;
-	BN_HIP(hipMalloc(&d_src, in_bytes + out_bytes));
-	void* d_dst = (char*)d_src + in_bytes;
-	int rc = BN_OK;
-	hipError_t e = hipMemcpyAsync(d_src, in, in_bytes, hipMemcpyHostToDevice, p->own_stream);
-	if (e == hipSuccess) rc = launch_fold(p, d_src, d_dst, round, arity, challenges, 1, p->own_stream);
-	if (e == hipSuccess && rc == BN_OK) e = hipMemcpyAsync(out, d_dst, out_bytes, hipMemcpyDeviceToHost, p->own_stream);
-	const hipError_t es = hipStreamSynchronize(p->own_stream);
-	if (e == hipSuccess) e = es;
-	(void)hipFree(d_src);  // on every path: nothing above returns between the allocation and here
-	if (rc != BN_OK) return rc;
-	if (e != hipSuccess) BN_FAIL(BN_ERR_HIP, "host fold failed: %s", hipGetErrorString(e));
-	return BN_OK;
+	DevBuf buf;
+	if (int rc = buf.alloc(in_bytes + out_bytes)) return rc;
+	void* d_dst = (char*)buf.p + in_bytes;
+	return staged_call(p->own_stream, in, buf.p, in_bytes, d_dst, out, out_bytes,
+	                   [&](hipStream_t st) { return launch_fold(p, buf.p, d_dst, round, arity, challenges, 1, st); });
 }

@@ -45,18 +45,11 @@ struct bn_antt_plan {
 
 namespace bn {
 // The argument checks of every *_device entry point (forward, inverse, fold): the plan, the buffers
-// and the batch, then (after the checks a call adds of its own) that the bytes read and the bytes
-// written do not overlap.
+// and the batch; each call then adds its own checks and BN_CHECK_IO_DISJOINT.
 inline int check_device_args(const bn_antt_plan* p, const void* d_in, const void* d_out, size_t batch) {
 	BN_CHECK_ARG(p != nullptr, "plan is NULL");
 	BN_CHECK_ARG(d_in != nullptr && d_out != nullptr, "device buffers must be non-NULL");
 	BN_CHECK_ARG(batch >= 1, "batch must be >= 1");
-	return BN_OK;
-}
-inline int check_no_overlap(const void* d_in, size_t in_bytes, const void* d_out, size_t out_bytes) {
-	const char* a = (const char*)d_in;
-	const char* b = (const char*)d_out;
-	BN_CHECK_ARG(a + in_bytes <= b || b + out_bytes <= a, "d_in and d_out must not overlap");
 	return BN_OK;
 }
 // hipEvent timing around one launch of pass `kind` (no-op unless plan->timing).

@@ -381,6 +381,17 @@ static std::vector<BbPass> bb_passes(const bn_bb31_ntt_plan* P, bool bitrev_in) 
 	return v;
 }
 
+// the device side of a new plan: the twiddle table, and the LDS attribute of every pass kernel
+static int bb_plan_to_device(bn_bb31_ntt_plan* P, const std::vector<uint32_t>& tab) {
+	BN_DEVICE_SCOPE(P->device);
+	if (int rc = dev_alloc(&P->wtab, tab.size() * sizeof(uint32_t))) return rc;
+	BN_HIP(hipMemcpy(P->wtab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+	for (const void* f : {pass_fn<0>(), pass_fn<1>(), pass_fn<2>(), pass_r_fn(0, 6), pass_r_fn(0, 7), pass_r_fn(0, 8),
+	                      pass_r_fn(0, 9), pass_r_fn(1, 6), pass_r_fn(1, 7), pass_r_fn(1, 8), pass_r_fn(1, 9)})
+		BN_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, ((1 << kMaxM) * kCols + (1 << 12)) * 4));
+	return BN_OK;
+}
+
 }  // namespace
 }  // namespace bn
 
@@ -431,17 +442,9 @@ extern "C" int bn_bb31_ntt_plan_create(int device, uint32_t generator, int log_g
 		}
 	}
 	(void)kR2;
-	DeviceScope ds(device);
-	hipError_t e = ds.err;
-	if (e == hipSuccess) e = hipMalloc(&P->wtab, tab.size() * sizeof(uint32_t));
-	if (e == hipSuccess) e = hipMemcpy(P->wtab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-	if (e == hipSuccess)
-		for (const void* f : {pass_fn<0>(), pass_fn<1>(), pass_fn<2>(), pass_r_fn(0, 6), pass_r_fn(0, 7), pass_r_fn(0, 8),
-		                      pass_r_fn(0, 9), pass_r_fn(1, 6), pass_r_fn(1, 7), pass_r_fn(1, 8), pass_r_fn(1, 9)})
-			if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, ((1 << kMaxM) * kCols + (1 << 12)) * 4);
-	if (e != hipSuccess) {
+	if (const int rc = bb_plan_to_device(P, tab)) {
 		bn_bb31_ntt_plan_destroy(P);
-		BN_FAIL(BN_ERR_HIP, "bb31 plan allocation failed: %s", hipGetErrorString(e));
+		return rc;
 	}
 	*out = P;
 	return BN_OK;
@@ -468,7 +471,8 @@ static int bb_forward(bn_bb31_ntt_plan* P, const uint32_t* d_in, uint32_t* d_out
 		if (P->scratch_words < n * batch) {
 			if (P->scratch) BN_HIP(hipFree(P->scratch));
 			P->scratch = nullptr;
-			BN_HIP(hipMalloc(&P->scratch, n * batch * sizeof(uint32_t)));
+			P->scratch_words = 0;
+			if (int rc = dev_alloc(&P->scratch, n * batch * sizeof(uint32_t))) return rc;
 			P->scratch_words = n * batch;
 		}
 		work = P->scratch;
@@ -509,9 +513,7 @@ extern "C" int bn_bb31_ntt_forward_device(bn_bb31_ntt_plan* P, const uint32_t* d
 	BN_CHECK_ARG(d_in != nullptr && d_out != nullptr, "device buffers must be non-NULL");
 	BN_CHECK_ARG(batch >= 1 && batch <= 65535, "batch must be in [1, 65535]");
 	const size_t bytes = ((size_t)4 << P->log_n) * batch;
-	const char* a = (const char*)d_in;
-	const char* b = (const char*)d_out;
-	BN_CHECK_ARG(a + bytes <= b || b + bytes <= a, "d_in and d_out must not overlap");
+	BN_CHECK_IO_DISJOINT(d_in, bytes, d_out, bytes);
 	BN_DEVICE_SCOPE(P->device);
 	return bb_forward(P, d_in, d_out, batch, in_bit_reversed, (hipStream_t)stream);
 }
@@ -525,12 +527,9 @@ extern "C" int bn_bb31_ntt_forward_host(bn_bb31_ntt_plan* P, const uint32_t* in,
 	const size_t n = (size_t)1 << P->log_n;
 	BN_CHECK_ARG(in_elems == n, "input has %zu elements, plan expects 2^%d", in_elems, P->log_n);
 	BN_DEVICE_SCOPE(P->device);
-	if (!P->h_dev) BN_HIP(hipMalloc(&P->h_dev, 2 * n * sizeof(uint32_t)));
+	if (!P->h_dev)
+		if (int rc = dev_alloc(&P->h_dev, 2 * n * sizeof(uint32_t))) return rc;
 	if (!P->own_stream) BN_HIP(hipStreamCreateWithFlags(&P->own_stream, hipStreamNonBlocking));
-	BN_HIP(hipMemcpyAsync(P->h_dev, in, n * 4, hipMemcpyHostToDevice, P->own_stream));
-	int rc = bb_forward(P, P->h_dev, P->h_dev + n, 1, in_bit_reversed, P->own_stream);
-	if (rc != BN_OK) return rc;
-	BN_HIP(hipMemcpyAsync(out, P->h_dev + n, n * 4, hipMemcpyDeviceToHost, P->own_stream));
-	BN_HIP(hipStreamSynchronize(P->own_stream));
-	return BN_OK;
+	return staged_call(P->own_stream, in, P->h_dev, n * 4, P->h_dev + n, out, n * 4,
+	                   [&](hipStream_t st) { return bb_forward(P, P->h_dev, P->h_dev + n, 1, in_bit_reversed, st); });
 }

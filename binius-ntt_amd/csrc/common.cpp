@@ -1,4 +1,4 @@
-// Thread-local error reporting and capability check for the C-ABI.
+// Thread-local error reporting, device allocation and capability check for the C-ABI.
 #include "common.hpp"
 
 #include <string.h>
@@ -15,6 +15,15 @@ void set_error(const char* fmt, ...) {
 }
 
 void clear_error() { g_err[0] = 0; }
+
+int dev_alloc(void** p, size_t bytes) {
+	const hipError_t e = hipMalloc(p, bytes);
+	if (e != hipSuccess) {
+		*p = nullptr;
+		BN_FAIL(BN_ERR_ALLOC, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+	}
+	return BN_OK;
+}
 
 }  // namespace bn
 

@@ -1,5 +1,6 @@
 // Shared host-side plumbing for the C-ABI: status codes, thread-local last error,
-// HIP error checking that reports instead of aborting.
+// HIP error checking that reports instead of aborting, the device guard, the owners of a device
+// allocation and of a per-call stream, and the staged (host in, device, host out) round trip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,8 +9,10 @@
 #include <stdio.h>
 
 #include <string>
+#include <utility>
 
 #include "binius_ntt_amd.h"
+#include "buf_check.hpp"
 
 namespace bn {
 
@@ -31,6 +34,13 @@ struct DeviceScope {
 	DeviceScope(const DeviceScope&) = delete;
 	DeviceScope& operator=(const DeviceScope&) = delete;
 };
+
+// The library's one device allocation: BN_ERR_ALLOC, with the size in the message, when it fails.
+int dev_alloc(void** p, size_t bytes);
+template <class T>
+int dev_alloc(T** p, size_t bytes) {
+	return dev_alloc((void**)p, bytes);
+}
 
 }  // namespace bn
 
@@ -59,3 +69,59 @@ struct DeviceScope {
 	do {                                             \
 		if (!(cond)) BN_FAIL(BN_ERR_INVALID, __VA_ARGS__); \
 	} while (0)
+
+// the bytes a *_device transform reads and the bytes it writes must share none (buf_check.hpp)
+#define BN_CHECK_IO_DISJOINT(d_in, in_bytes, d_out, out_bytes) \
+	BN_CHECK_ARG(!::bn::ranges_overlap((d_in), (in_bytes), (d_out), (out_bytes)), "d_in and d_out must not overlap")
+
+namespace bn {
+
+// A device allocation that is freed on the way out unless release() hands it to a plan or prover.
+struct DevBuf {
+	void* p = nullptr;
+	DevBuf() = default;
+	DevBuf(const DevBuf&) = delete;
+	DevBuf& operator=(const DevBuf&) = delete;
+	~DevBuf() {
+		if (p) (void)hipFree(p);
+	}
+	int alloc(size_t bytes) { return dev_alloc(&p, bytes); }
+	void* release() { return std::exchange(p, nullptr); }
+};
+
+// A non-blocking stream that lives for one call.
+struct CallStream {
+	hipStream_t s = nullptr;
+	CallStream() = default;
+	CallStream(const CallStream&) = delete;
+	CallStream& operator=(const CallStream&) = delete;
+	~CallStream() {
+		if (s) (void)hipStreamDestroy(s);
+	}
+	int create() {
+		BN_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+		return BN_OK;
+	}
+};
+
+// Host in -> device -> host out, synchronous, on `st`: in_bytes of `in` are copied to d_in (nothing
+// when in_bytes is 0), `launch(st)` queues the work and returns a BN_* code, out_bytes of d_out are
+// copied to `out` (d_in and d_out may lie in one allocation). The first failure stops the queueing
+// and is the one reported; the stream is synchronised on every path, so on return it is idle: the
+// device buffers may be freed and the caller's host memory is touched no more.
+template <class Launch>
+int staged_call(hipStream_t st, const void* in, void* d_in, size_t in_bytes, const void* d_out, void* out, size_t out_bytes,
+                Launch launch) {
+	const int rc = [&]() -> int {
+		if (in_bytes) BN_HIP(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, st));
+		if (int r = launch(st)) return r;
+		BN_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+		return BN_OK;
+	}();
+	const hipError_t es = hipStreamSynchronize(st);
+	if (rc != BN_OK) return rc;
+	if (es != hipSuccess) BN_FAIL(BN_ERR_HIP, "hipStreamSynchronize after a staged call -> %s", hipGetErrorString(es));
+	return BN_OK;
+}
+
+}  // namespace bn

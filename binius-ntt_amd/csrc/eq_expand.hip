@@ -34,10 +34,10 @@
 // Bitsliced output queues the in-place k_bitslice launch (field.hip) behind the last pass.
 #include <hip/hip_runtime.h>
 
-#include "antt_bs_dev.hpp"  // st_stream
 #include "common.hpp"
 #include "eq_plan.hpp"
 #include "gf128_rtab.hpp"
+#include "stream_io.hpp"
 
 int bitslice_launch(const void* src, void* dst, size_t nblk, int untranspose, hipStream_t st);  // field.hip
 
@@ -117,8 +117,6 @@ __global__ __launch_bounds__(kEqThreads) void eq_expand_pass(EqParams P) {
 	}
 }
 
-static uint4 words4(const uint32_t* w) { return make_uint4(w[0], w[1], w[2], w[3]); }
-
 // Every pass of the plan on `st`, then the bit transpose. Arguments are checked by the caller; the
 // current device is the buffer's.
 static int eq_launch(int num_vars, const EqPlan& plan, const uint32_t* challenges, const uint32_t* scale, uint4* d_out,
@@ -184,23 +182,13 @@ extern "C" int bn_eq_expand_host(int device, int num_vars, const uint32_t* chall
 	if (int rc = eq_check(num_vars, challenges, out, bitsliced, 0, &plan)) return rc;
 	BN_DEVICE_SCOPE(device);
 	const size_t bytes = (size_t)16 << num_vars;
-	// staged per call: the size depends on num_vars
-	void* d_buf = nullptr;
-	if (hipMalloc(&d_buf, bytes) != hipSuccess) BN_FAIL(BN_ERR_ALLOC, "hipMalloc of %zu bytes failed", bytes);
-	hipStream_t st = nullptr;
-	hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-	int rc = BN_OK;
-	if (e == hipSuccess) rc = eq_launch(num_vars, plan, challenges, scale, (uint4*)d_buf, bitsliced, st);
-	if (e == hipSuccess && rc == BN_OK) e = hipMemcpyAsync(out, d_buf, bytes, hipMemcpyDeviceToHost, st);
-	if (st) {
-		const hipError_t es = hipStreamSynchronize(st);
-		if (e == hipSuccess) e = es;
-		(void)hipStreamDestroy(st);
-	}
-	(void)hipFree(d_buf);  // on every path: nothing above returns between the allocation and here
-	if (rc != BN_OK) return rc;
-	if (e != hipSuccess) BN_FAIL(BN_ERR_HIP, "host expansion failed: %s", hipGetErrorString(e));
-	return BN_OK;
+	// staged per call (no input: the challenges travel in the launches): the size depends on num_vars
+	DevBuf buf;
+	CallStream cs;
+	if (int rc = buf.alloc(bytes)) return rc;
+	if (int rc = cs.create()) return rc;
+	return staged_call(cs.s, nullptr, nullptr, 0, buf.p, out, bytes,
+	                   [&](hipStream_t st) { return eq_launch(num_vars, plan, challenges, scale, (uint4*)buf.p, bitsliced, st); });
 }
 
 extern "C" int bn_eq_expand_passes(int num_vars, int max_levels, int32_t* levels, size_t cap, int* n_passes) {

@@ -15,6 +15,8 @@ namespace bn {
 constexpr int kRTabEntries = 32 * 16;  // uint4 entries of one constant's table
 
 __device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }
+// a GF(2^128) element from its four words (host side: the launch constants travel by value)
+inline uint4 words4(const uint32_t* w) { return make_uint4(w[0], w[1], w[2], w[3]); }
 
 // r * x from r's nibble table T[32][16]
 __device__ __forceinline__ uint4 fold_mul_r(const uint4* T, uint4 x) {

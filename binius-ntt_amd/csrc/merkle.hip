@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "merkle_plan.hpp"
 #include "sha256_dev.hpp"
+#include "stream_io.hpp"
 
 namespace bn {
 
@@ -36,12 +37,6 @@ static_assert(2 * kMkThreads == 1 << kMkRowGroupLog, "one lane a node of the fir
 static_assert(kMkThreads >> (kMkRowsPerPass - 1) >= 64, "a fused row fills a wave");
 static_assert(mk_leaf_lds_words(kMkMaxLeafLog) * 4 <= kMkLdsPerGroup && mk_row_lds_words() * 4 <= kMkLdsPerGroup, "static LDS");
 
-typedef unsigned int mk_u32x4 __attribute__((ext_vector_type(4)));
-// streaming 16-byte load: the codeword is read once
-__device__ __forceinline__ uint4 mk_ld_stream(const uint4* p) {
-	const mk_u32x4 v = __builtin_nontemporal_load((const mk_u32x4*)p);
-	return make_uint4(v.x, v.y, v.z, v.w);
-}
 __device__ __forceinline__ uint32_t mk_bswap(uint32_t x) { return __builtin_bswap32(x); }
 __device__ __forceinline__ uint4 mk_bswap4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
 	return make_uint4(mk_bswap(a), mk_bswap(b), mk_bswap(c), mk_bswap(d));
@@ -114,7 +109,8 @@ __global__ __launch_bounds__(kMkThreads) void merkle_leaf_pass(MkLeafParams P) {
 		for (int i = 0; i < C4; i++) {
 			const uint32_t x = i * 64 + lane;  // consecutive lanes, consecutive 16 bytes of the run
 			const uint64_t leaf = wave_leaf + x / C4;
-			g[i] = leaf < n_leaves ? mk_ld_stream(P.data + leaf * E + (uint64_t)ch * C4 + x % C4) : make_uint4(0, 0, 0, 0);
+			// streaming: the codeword is read once
+			g[i] = leaf < n_leaves ? ld_stream((const uint32_t*)(P.data + leaf * E + (uint64_t)ch * C4 + x % C4)) : make_uint4(0, 0, 0, 0);
 		}
 	};
 
@@ -270,12 +266,6 @@ static int mk_launch(const MkPlan& plan, const void* d_data, int log_leaves, int
 	return BN_OK;
 }
 
-static bool mk_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-	return x < y + nb && y < x + na;
-}
-static bool mk_aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
-
 static int mk_check_shape(int log_leaves, int log_leaf_elems) {
 	BN_CHECK_ARG(log_leaf_elems >= 0 && log_leaf_elems <= kMkMaxLeafLog, "log_leaf_elems must be in [0, %d] (got %d)", kMkMaxLeafLog,
 	             log_leaf_elems);
@@ -289,8 +279,8 @@ static int mk_check_commit(const void* data, int log_leaves, int log_leaf_elems,
 	BN_CHECK_ARG(data != nullptr && tree != nullptr, "NULL buffer");
 	if (int rc = mk_check_shape(log_leaves, log_leaf_elems)) return rc;
 	BN_CHECK_ARG(mk_plan(log_leaves, log_leaf_elems, max_rows, plan), "max_rows must be in [0, %d] (got %d)", kMkRowsPerPass, max_rows);
-	BN_CHECK_ARG(!device || (mk_aligned(data, 16) && mk_aligned(tree, 16)), "the buffers must be 16-byte aligned");
-	BN_CHECK_ARG(!mk_overlap(data, (uint64_t)16 << (log_leaves + log_leaf_elems), tree, 32 * mk_tree_digests(log_leaves)),
+	BN_CHECK_ARG(!device || (is_aligned(data, 16) && is_aligned(tree, 16)), "the buffers must be 16-byte aligned");
+	BN_CHECK_ARG(!ranges_overlap(data, (uint64_t)16 << (log_leaves + log_leaf_elems), tree, 32 * mk_tree_digests(log_leaves)),
 	             "the data and the tree overlap");
 	return BN_OK;
 }
@@ -338,24 +328,13 @@ extern "C" int bn_merkle_commit_host(int device, const uint32_t* data, int log_l
 	BN_DEVICE_SCOPE(device);
 	const size_t data_bytes = (size_t)16 << (log_leaves + log_leaf_elems), tree_bytes = (size_t)(32 * mk_tree_digests(log_leaves));
 	// staged per call, data and tree in one allocation (both sizes are multiples of 16)
-	void* d_buf = nullptr;
-	if (hipMalloc(&d_buf, data_bytes + tree_bytes) != hipSuccess) BN_FAIL(BN_ERR_ALLOC, "hipMalloc of %zu bytes failed", data_bytes + tree_bytes);
-	void* d_tree = (uint8_t*)d_buf + data_bytes;
-	hipStream_t st = nullptr;
-	hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-	int rc = BN_OK;
-	if (e == hipSuccess) e = hipMemcpyAsync(d_buf, data, data_bytes, hipMemcpyHostToDevice, st);
-	if (e == hipSuccess) rc = mk_launch(plan, d_buf, log_leaves, log_leaf_elems, d_tree, st);
-	if (e == hipSuccess && rc == BN_OK) e = hipMemcpyAsync(tree, d_tree, tree_bytes, hipMemcpyDeviceToHost, st);
-	if (st) {
-		const hipError_t es = hipStreamSynchronize(st);
-		if (e == hipSuccess) e = es;
-		(void)hipStreamDestroy(st);
-	}
-	(void)hipFree(d_buf);  // on every path: nothing above returns between the allocation and here
-	if (rc != BN_OK) return rc;
-	if (e != hipSuccess) BN_FAIL(BN_ERR_HIP, "host commitment failed: %s", hipGetErrorString(e));
-	return BN_OK;
+	DevBuf buf;
+	CallStream cs;
+	if (int rc = buf.alloc(data_bytes + tree_bytes)) return rc;
+	if (int rc = cs.create()) return rc;
+	void* d_tree = (uint8_t*)buf.p + data_bytes;
+	return staged_call(cs.s, data, buf.p, data_bytes, d_tree, tree, tree_bytes,
+	                   [&](hipStream_t st) { return mk_launch(plan, buf.p, log_leaves, log_leaf_elems, d_tree, st); });
 }
 
 extern "C" int bn_merkle_open_device(const void* d_data, const void* d_tree, int log_leaves, int log_leaf_elems, const uint32_t* d_indices,
@@ -364,12 +343,12 @@ extern "C" int bn_merkle_open_device(const void* d_data, const void* d_tree, int
 	if (int rc = mk_check_shape(log_leaves, log_leaf_elems)) return rc;
 	const uint64_t rec = mk_open_bytes(log_leaves, log_leaf_elems);
 	BN_CHECK_ARG(n_queries >= 1 && n_queries <= ((uint64_t)1 << 40) / rec, "n_queries must be in [1, 2^40 / record bytes] (got %zu)", n_queries);
-	BN_CHECK_ARG(mk_aligned(d_data, 16) && mk_aligned(d_tree, 16) && mk_aligned(d_out, 16) && mk_aligned(d_indices, 4),
+	BN_CHECK_ARG(is_aligned(d_data, 16) && is_aligned(d_tree, 16) && is_aligned(d_out, 16) && is_aligned(d_indices, 4),
 	             "the buffers must be 16-byte aligned, the indices 4-byte");
 	const uint64_t data_bytes = (uint64_t)16 << (log_leaves + log_leaf_elems), tree_bytes = 32 * mk_tree_digests(log_leaves);
-	BN_CHECK_ARG(!mk_overlap(d_data, data_bytes, d_tree, tree_bytes), "the data and the tree overlap");
-	BN_CHECK_ARG(!mk_overlap(d_out, n_queries * rec, d_data, data_bytes) && !mk_overlap(d_out, n_queries * rec, d_tree, tree_bytes) &&
-	                 !mk_overlap(d_out, n_queries * rec, d_indices, 4 * (uint64_t)n_queries),
+	BN_CHECK_ARG(!ranges_overlap(d_data, data_bytes, d_tree, tree_bytes), "the data and the tree overlap");
+	BN_CHECK_ARG(!ranges_overlap(d_out, n_queries * rec, d_data, data_bytes) && !ranges_overlap(d_out, n_queries * rec, d_tree, tree_bytes) &&
+	                 !ranges_overlap(d_out, n_queries * rec, d_indices, 4 * (uint64_t)n_queries),
 	             "the output overlaps the data, the tree or the indices");
 	MkOpenParams prm{(const uint4*)d_data, (const uint4*)d_tree, d_indices, (uint4*)d_out, (unsigned long long)n_queries, log_leaves, log_leaf_elems};
 	const unsigned grid = (unsigned)(n_queries < (1u << 20) ? n_queries : (1u << 20));

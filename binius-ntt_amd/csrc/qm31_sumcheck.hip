@@ -188,6 +188,27 @@ static unsigned grid_for(const bn_qm31_sumcheck* S, size_t items) {
 	return (unsigned)std::max<size_t>(1, std::min<size_t>(want, (size_t)S->cus * S->wg_per_cu));
 }
 
+// the device side of a new prover, on the current device: stream, columns (reduced), accumulators
+static int qm_setup(bn_qm31_sumcheck* S, const uint32_t* evals) {
+	const size_t words = 2 * S->cur * 4;
+	BN_HIP(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
+	if (int rc = dev_alloc(&S->cols, words * 4)) return rc;
+	if (int rc = dev_alloc(&S->acc, 24 * sizeof(unsigned long long))) return rc;
+	BN_HIP(hipMemsetAsync(S->acc, 0, 24 * sizeof(unsigned long long), S->stream));
+	BN_HIP(hipHostMalloc(&S->h_acc, 12 * sizeof(unsigned long long), hipHostMallocDefault));
+	BN_HIP(hipMemcpyAsync(S->cols, evals, words * 4, hipMemcpyHostToDevice, S->stream));
+	int cus = 0;
+	if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, S->device) == hipSuccess) S->cus = std::max(cus, 1);
+#ifdef BN_DEV
+	if (const char* v = getenv("BN_QM_WG_PER_CU")) S->wg_per_cu = std::max(1, atoi(v));  // tuning, development build only
+#endif
+	// QM31(uint32_t) assumes values < p; reduce whatever was passed
+	hipLaunchKernelGGL(qm_reduce, dim3(grid_for(S, words)), dim3(kT), 0, S->stream, S->cols, words);
+	BN_HIP(hipGetLastError());
+	BN_HIP(hipStreamSynchronize(S->stream));
+	return BN_OK;
+}
+
 }  // namespace
 }  // namespace bn
 
@@ -206,28 +227,9 @@ extern "C" int bn_qm31_sumcheck_create(int device, int num_vars, const uint32_t*
 	S->device = device;
 	S->num_vars = num_vars;
 	S->cur = (size_t)1 << num_vars;
-	const size_t words = 2 * S->cur * 4;
-	hipError_t e = hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking);
-	if (e == hipSuccess) e = hipMalloc(&S->cols, words * 4);
-	if (e == hipSuccess) e = hipMalloc(&S->acc, 24 * sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipMemsetAsync(S->acc, 0, 24 * sizeof(unsigned long long), S->stream);
-	if (e == hipSuccess) e = hipHostMalloc(&S->h_acc, 12 * sizeof(unsigned long long), hipHostMallocDefault);
-	if (e == hipSuccess) e = hipMemcpyAsync(S->cols, evals, words * 4, hipMemcpyHostToDevice, S->stream);
-	int cus = 0;
-	if (e == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess)
-		S->cus = std::max(cus, 1);
-#ifdef BN_DEV
-	if (const char* v = getenv("BN_QM_WG_PER_CU")) S->wg_per_cu = std::max(1, atoi(v));  // tuning, development build only
-#endif
-	if (e == hipSuccess) {
-		// QM31(uint32_t) assumes values < p; reduce whatever was passed
-		hipLaunchKernelGGL(qm_reduce, dim3(grid_for(S, words)), dim3(kT), 0, S->stream, S->cols, words);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(S->stream);
-	if (e != hipSuccess) {
+	if (const int rc = qm_setup(S, evals)) {
 		bn_qm31_sumcheck_destroy(S);
-		BN_FAIL(BN_ERR_HIP, "qm31 sumcheck setup failed: %s", hipGetErrorString(e));
+		return rc;
 	}
 	*out = S;
 	return BN_OK;

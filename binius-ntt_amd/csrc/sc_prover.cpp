@@ -34,12 +34,6 @@ struct ScFree {
 };
 using ScOwner = std::unique_ptr<bn_sumcheck, ScFree>;
 
-// a device allocation that is freed unless released into the prover
-struct HipFree {
-	void operator()(uint32_t* p) const { (void)hipFree(p); }
-};
-using DevWords = std::unique_ptr<uint32_t, HipFree>;
-
 int check_shape(int num_vars, int d, int transposed) {
 	BN_CHECK_ARG(d >= 1 && d <= kMaxD, "composition_size must be in [1, %d]", kMaxD);
 	BN_CHECK_ARG(num_vars >= 1 && num_vars <= 30, "num_vars must be in [1, 30]");
@@ -62,7 +56,7 @@ int sc_new(int device, int num_vars, int d, size_t col_words, ScOwner& out) {
 	sc->num_vars = num_vars;
 	sc->d = d;
 	BN_HIP(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
-	BN_HIP(hipMalloc(&sc->acc, sizeof(uint32_t) * 2 * kAccSet));
+	if (const int rc = dev_alloc(&sc->acc, sizeof(uint32_t) * 2 * kAccSet)) return rc;
 	BN_HIP(hipMemsetAsync(sc->acc, 0, sizeof(uint32_t) * 2 * kAccSet, sc->stream));
 	BN_HIP(hipHostMalloc((void**)&sc->h_res, sizeof(uint32_t) * (kResSeq + 1), hipHostMallocMapped | hipHostMallocCoherent));
 	memset(sc->h_res, 0, sizeof(uint32_t) * (kResSeq + 1));
@@ -70,7 +64,7 @@ int sc_new(int device, int num_vars, int d, size_t col_words, ScOwner& out) {
 	if (const int rc = sc_kernels_init(sc.get())) return rc;
 	if (col_words) {
 		sc->col_words = col_words;
-		BN_HIP(hipMalloc(&sc->cols, sizeof(uint32_t) * col_words * (size_t)d));
+		if (const int rc = dev_alloc(&sc->cols, sizeof(uint32_t) * col_words * (size_t)d)) return rc;
 	}
 	out = std::move(sc);
 	return BN_OK;
@@ -234,16 +228,16 @@ extern "C" int bn_sumcheck_set_shard(bn_sumcheck* sc, int rank, int world) {
 	// keep the batches b with b mod world == rank, in order
 	const size_t n = (size_t)1 << sc->num_vars;
 	const size_t nb_local = n / 32 / world;
-	uint32_t* p = nullptr;
-	BN_HIP(hipMalloc(&p, sizeof(uint32_t) * 128 * nb_local * (size_t)sc->d));
-	DevWords local(p);
+	DevBuf local;  // freed unless released into the prover
+	if ((rc = local.alloc(sizeof(uint32_t) * 128 * nb_local * (size_t)sc->d)) != BN_OK) return rc;
+	uint32_t* const p = (uint32_t*)local.p;
 	for (int j = 0; j < sc->d; j++)
 		BN_HIP(hipMemcpy2DAsync(p + (size_t)j * 128 * nb_local, 128 * sizeof(uint32_t),
 		                        sc->cols + (size_t)j * sc->col_words + 128 * (size_t)rank, 128 * sizeof(uint32_t) * world,
 		                        128 * sizeof(uint32_t), nb_local, hipMemcpyDeviceToDevice, sc->stream));
 	BN_HIP(hipStreamSynchronize(sc->stream));
 	BN_HIP(hipFree(sc->cols));
-	sc->cols = local.release();
+	sc->cols = (uint32_t*)local.release();
 	sc->col_words = 128 * nb_local;
 	sc->cur = n / world;
 	sc->rank = rank;
@@ -281,13 +275,12 @@ extern "C" int bn_sumcheck_import_gathered(bn_sumcheck* sc, const uint32_t* word
 	for (int r = 0; r < world; r++)
 		for (int j = 0; j < sc->d; j++)
 			memcpy(&host[(size_t)j * col_words + 128 * (size_t)r], words + ((size_t)r * sc->d + j) * 128, 128 * sizeof(uint32_t));
-	uint32_t* p = nullptr;
-	BN_HIP(hipMalloc(&p, sizeof(uint32_t) * host.size()));
-	DevWords cols(p);
-	BN_HIP(hipMemcpyAsync(p, host.data(), sizeof(uint32_t) * host.size(), hipMemcpyHostToDevice, sc->stream));
+	DevBuf cols;  // freed unless released into the prover
+	if (const int rc = cols.alloc(sizeof(uint32_t) * host.size())) return rc;
+	BN_HIP(hipMemcpyAsync(cols.p, host.data(), sizeof(uint32_t) * host.size(), hipMemcpyHostToDevice, sc->stream));
 	BN_HIP(hipStreamSynchronize(sc->stream));
 	BN_HIP(hipFree(sc->cols));
-	sc->cols = cols.release();
+	sc->cols = (uint32_t*)cols.release();
 	sc->col_words = col_words;
 	sc->cur = (size_t)32 * world;
 	sc->rank = 0;

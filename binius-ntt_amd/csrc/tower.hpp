@@ -48,17 +48,10 @@ __host__ __device__ constexpr uint64_t tw_inv(uint64_t a, int h) {
 	return tw_mul(dinv, inter, h - 1) | (tw_mul(dinv, a1, h - 1) << half);
 }
 
-// GF(2^128) as (lo, hi) u64 pair; schoolbook top level like tower_height_7_mul
-// (src/ulvt/sumcheck/test/utils/tower_7_mul.cu:4-20), Karatsuba below.
+// GF(2^128) as (lo, hi) u64 pair (tw_mul128_host below)
 struct u128p {
 	uint64_t lo, hi;
 };
-__host__ __device__ inline u128p tw_mul128(u128p a, u128p b) {
-	const uint64_t z0 = tw_mul(a.lo, b.lo, 6);
-	const uint64_t z2 = tw_mul(a.hi, b.hi, 6);
-	const uint64_t z1 = tw_mul(a.lo ^ a.hi, b.lo ^ b.hi, 6) ^ z0 ^ z2;
-	return u128p{z0 ^ z2, z1 ^ tw_mul_alpha(z2, 6)};
-}
 
 // Host-only fast path (round claims, interpolation): the Karatsuba recursion stops at GF(2^8),
 // whose products come from a 64 KiB table (built on first use), so a GF(2^128) product is 27
@@ -99,15 +92,7 @@ __host__ inline uint64_t tw_mul_h(const uint8_t* tab, uint64_t a, uint64_t b) {
 		return (z0 ^ z2) | ((z1 ^ tw_alpha_h<H - 1>(z2)) << half);
 	}
 }
-__host__ inline uint64_t tw_mul_host(uint64_t a, uint64_t b, int h) {
-	const uint8_t* tab = tw_mul8_table();
-	switch (h) {
-		case 4: return tw_mul_h<4>(tab, a, b);
-		case 5: return tw_mul_h<5>(tab, a, b);
-		case 6: return tw_mul_h<6>(tab, a, b);
-		default: return h <= 3 ? tw_mul_h<3>(tab, a, b) : tw_mul(a, b, h);
-	}
-}
+// schoolbook top level like tower_height_7_mul (src/ulvt/sumcheck/test/utils/tower_7_mul.cu:4-20)
 __host__ inline u128p tw_mul128_host(u128p a, u128p b) {
 	const uint8_t* tab = tw_mul8_table();
 	const uint64_t z0 = tw_mul_h<6>(tab, a.lo, b.lo);

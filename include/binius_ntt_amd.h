@@ -29,10 +29,13 @@ extern "C" {
 enum {
 	BN_OK = 0,
 	BN_ERR_INVALID = 1,     /* bad argument (reference: ASSERT / apply() returning false) */
-	BN_ERR_HIP = 2,         /* HIP runtime failure (reference: CUDA_CHECK, common.cuh:18-29) */
+	BN_ERR_HIP = 2,         /* HIP runtime failure other than an allocation (reference: CUDA_CHECK, common.cuh:18-29) */
 	BN_ERR_UNSUPPORTED = 3, /* valid in the reference surface but not built here */
-	BN_ERR_ALLOC = 4        /* device or host allocation failure */
+	BN_ERR_ALLOC = 4        /* device or host allocation failure: every device allocation of a plan, a
+	                           prover or a host call's staging reports it, with the size in bn_last_error() */
 };
+/* The *_host calls are synchronous on every path: when one returns, with whatever status, no copy
+ * from or to the caller's buffers is still queued. */
 
 /* Description of the last error on this thread ("" if none). */
 const char* bn_last_error(void);

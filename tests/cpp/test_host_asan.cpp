@@ -8,8 +8,9 @@
 //     AdditiveNTTConf, BB31, QM31/interpolate_at) against the oracle;
 //   * the library's host-side code: the generated bitsliced circuits behind multiply_unrolled<H>,
 //     the packed-subfield helpers, bn_sumcheck_interpolate, the sumcheck round planner
-//     (csrc/sc_rounds.cpp) over every round shape, and the argument-checking / error paths of the
-//     C-ABI (no device present here: they must fail cleanly with a status code);
+//     (csrc/sc_rounds.cpp) over every round shape, the buffer checks (csrc/buf_check.hpp), and the
+//     argument-checking / error paths of the C-ABI, the staged host calls among them (no device
+//     present here: they must fail cleanly with a status code and leak nothing);
 //   * all 14 generated circuits of csrc/bitsliced_gen.hpp, compiled into this program, through
 //     the conformance routine of circuit_conformance.hpp with a small trial count: every alias
 //     mode, every operand in a heap allocation of exactly its documented size, so a gate that
@@ -34,6 +35,7 @@
 #include "utils/bitslicing.hpp"
 #include "utils/common.hpp"
 #include "../../oracle/oracle.h"
+#include "buf_check.hpp"
 #include "circuit_conformance.hpp"
 #include "sc_rounds.hpp"
 
@@ -423,10 +425,64 @@ static void library_host_checks() {
 	}
 }
 
+// The buffer checks of the entry points (csrc/buf_check.hpp, host only), then the entry points that
+// use them and the staged host calls, through the C ABI with no device present.
+static void buffer_check_checks() {
+	using bn::is_aligned;
+	using bn::ranges_overlap;
+	const auto at = [](uintptr_t a) { return reinterpret_cast<const void*>(a); };
+	check(!ranges_overlap(at(0x1000), 0x100, at(0x2000), 0x100) && !ranges_overlap(at(0x2000), 0x100, at(0x1000), 0x100),
+	      "ranges_overlap: disjoint ranges");
+	check(!ranges_overlap(at(0x1000), 0x100, at(0x1100), 0x100) && !ranges_overlap(at(0x1100), 0x100, at(0x1000), 0x100),
+	      "ranges_overlap: adjacent ranges do not overlap");
+	check(ranges_overlap(at(0x1000), 0x100, at(0x10ff), 0x100) && ranges_overlap(at(0x10ff), 0x100, at(0x1000), 0x100),
+	      "ranges_overlap: one shared byte");
+	check(ranges_overlap(at(0x1000), 0x1000, at(0x1800), 0x10) && ranges_overlap(at(0x1800), 0x10, at(0x1000), 0x1000),
+	      "ranges_overlap: nested ranges");
+	check(ranges_overlap(at(0x1000), 0x100, at(0x1000), 0x100), "ranges_overlap: identical ranges");
+	check(!ranges_overlap(at(0x1000), 0, at(0x1000), 0x100) && !ranges_overlap(at(0x1000), 0x100, at(0x1080), 0) &&
+	          !ranges_overlap(at(0x1000), 0, at(0x1000), 0),
+	      "ranges_overlap: a zero-length range overlaps nothing");
+	// (the pointer form a + n <= b wrapped to 0 here and called the ranges disjoint or not by accident)
+	check(!ranges_overlap(at(UINTPTR_MAX - 15), 16, at(0x1000), 0x100) && !ranges_overlap(at(0x1000), 0x100, at(UINTPTR_MAX - 15), 16) &&
+	          ranges_overlap(at(UINTPTR_MAX - 15), 16, at(UINTPTR_MAX - 31), 17) && !ranges_overlap(at(UINTPTR_MAX - 15), 16, at(UINTPTR_MAX - 31), 16),
+	      "ranges_overlap: a range ending at the highest address does not wrap");
+	check(is_aligned(at(0x1000), 4) && is_aligned(at(0x1004), 4) && !is_aligned(at(0x1002), 4) && !is_aligned(at(0x1001), 4),
+	      "is_aligned: 4 bytes");
+	check(is_aligned(at(0x1000), 16) && is_aligned(at(0x1010), 16) && !is_aligned(at(0x1008), 16) && !is_aligned(at(0x100f), 16),
+	      "is_aligned: 16 bytes");
+
+	// the device entry points check their buffers before they touch the device: made-up addresses do
+	alignas(16) static uint8_t mem[4096];
+	uint8_t* const data = mem;          // 2^2 leaves of 2^0 elements: 64 bytes of data, 7 digests
+	uint8_t* const tree = mem + 1024;
+	uint32_t* const idx = reinterpret_cast<uint32_t*>(mem + 2048);
+	check(bn_merkle_commit_device(data, 2, 0, data + 48, nullptr) == BN_ERR_INVALID && std::strlen(bn_last_error()) > 0,
+	      "bn_merkle_commit_device rejects overlapping data and tree");
+	check(bn_merkle_commit_device(data, 2, 0, tree + 8, nullptr) == BN_ERR_INVALID, "bn_merkle_commit_device rejects a misaligned tree");
+	check(bn_merkle_open_device(data, tree, 2, 0, idx, 4, idx, nullptr) == BN_ERR_INVALID,
+	      "bn_merkle_open_device rejects an output that overlaps the indices");
+	check(bn_merkle_open_device(data, tree, 2, 0, reinterpret_cast<uint32_t*>(mem + 2050), 4, mem + 3072, nullptr) == BN_ERR_INVALID,
+	      "bn_merkle_open_device rejects misaligned indices");
+	uint32_t r[4 * 31] = {0}, one[4] = {0};
+	check(bn_eq_expand_host(0, 31, r, nullptr, 0, one) == BN_ERR_INVALID, "bn_eq_expand_host rejects num_vars 31");
+	check(bn_merkle_commit_host(0, one, 0, 9, mem) == BN_ERR_INVALID, "bn_merkle_commit_host rejects log_leaf_elems 9");
+	check(bn_antt_fri_fold_host(nullptr, one, 1, 0, 1, r, one) == BN_ERR_INVALID, "bn_antt_fri_fold_host rejects a NULL plan");
+
+	// valid staged calls with no device: a status code and a message, nothing leaked (leak detection is on)
+	int rc = bn_eq_expand_host(0, 0, nullptr, nullptr, 0, one);
+	check(rc != BN_OK && std::strlen(bn_last_error()) > 0, "bn_eq_expand_host without a device fails cleanly");
+	uint32_t leaf[4] = {1, 2, 3, 4};
+	uint8_t root[32];
+	rc = bn_merkle_commit_host(0, leaf, 0, 0, root);
+	check(rc != BN_OK && std::strlen(bn_last_error()) > 0, "bn_merkle_commit_host without a device fails cleanly");
+}
+
 int main() {
 	oracle_checks();
 	mirror_checks();
 	library_host_checks();
+	buffer_check_checks();
 	sumcheck_planner_checks();
 	failures += conformance::run_all(2);
 	std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "PASSED", failures);
