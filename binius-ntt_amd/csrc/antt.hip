@@ -189,21 +189,24 @@ static int launch_v0(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, 
 	return BN_OK;
 }
 
-// Kernel variants: 0 compact tiles (log_h < 12), 1 bitsliced LDS tiles (antt_bs_pass), 4 bitsliced
-// register tiles (antt_rr_pass), 5 = 4 for the passes whose twiddles all lie in GF(2^8) and 1 for
-// the others (the default for log_h >= 12).
-static bool valid_variant(int v) { return v == 0 || v == 1 || v == 4 || v == 5; }
+const void* ntt_kernel_fn(int instance) {
+	const NttFamily f = kNttInstances[instance].family;
+	return f == NttFamily::Rr ? rr_kernel_fn(instance) : f == NttFamily::InvBs ? inv_kernel_fn(instance) : bs_kernel_fn(instance);
+}
 
-// development build only (make BN_DEV=1): BN_ANTT_VARIANT overrides the default kernel of new plans
-static void dev_variant_override(bn_antt_plan* p) {
-#ifdef BN_DEV
-	if (const char* e = getenv("BN_ANTT_VARIANT")) {
-		const int v = atoi(e);
-		if (v != 0 && valid_variant(v)) p->variant = v;
-	}
-#else
-	(void)p;
-#endif
+// A plan's setup for the bitsliced fast path (bs_supports), on creation and on the first change from variant 0
+static int bs_prepare(bn_antt_plan* plan) {
+	for (int i = 0; i < kNttInstanceCount; i++)
+		BN_HIP(hipFuncSetAttribute(ntt_kernel_fn(i), hipFuncAttributeMaxDynamicSharedMemorySize, (int)instance_lds_bytes(kNttInstances[i])));
+	// the pass tables are built here, once per plan, so that a table the kernels cannot run (a bottom
+	// tile that is not one contiguous run, stage bits that are not the top tile bits) fails the plan
+	// and never reaches a launch
+	int rc = plan_pass_tables(plan->log_h, plan->log_rate, plan->s_host, plan->passes, plan->rt);
+	if (rc != BN_OK) return rc;
+	int cus = 0;
+	BN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, plan->device));
+	plan->num_cus = std::max(cus, 1);
+	return BN_OK;
 }
 
 // the device side of a new plan: the subspace table, and the pass tables where the fast path applies
@@ -213,7 +216,7 @@ static int plan_to_device(bn_antt_plan* p) {
 	if (!p->s_host.empty()) BN_HIP(hipMemcpy(p->s_dev, p->s_host.data(), p->s_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
 	if (bs_supports(p->log_h, p->log_rate)) {
 		if (int rc = bs_prepare(p)) return rc;
-		dev_variant_override(p);
+		p->variant = bs_dev_knobs().variant;  // 5 (mixed register and LDS tiles) outside the development build
 	}
 	return BN_OK;
 }

@@ -30,12 +30,11 @@
 // layout is never restored: the host tabulates the twiddle words for the rotated bit-lane meaning
 // (BsPass::pat2), and after stage 0 the transposed pair is written straight to its compact slots.
 //
-// This file: the two kernel families (antt_bs_pass, antt_bs3_pass), the choice of a kernel per pass
-// and launch (select_pass), the launches, and the development build's trace and timing. The pass
-// split and every table are planned on the host in antt_passes.cpp and cached in the plan.
+// This file: the two kernel families (antt_bs_pass, antt_bs3_pass), their instances of the list in
+// antt_passes.hpp, the launches, and the development build's trace and timing. The pass split, every
+// table and the kernel of every launch are planned on the host in antt_passes.cpp.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdio>
 #include <type_traits>
 #include <vector>
@@ -78,6 +77,7 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 	// stages in its loop it spills 28 (L = 4) and 23 (L = 1) VGPRs against 9 and 5
 	constexpr bool packed = ROLE == ROLE_LAST;
 	static_assert(FMAX == 8 || FMAX == 32, "early_u_words is sized for the register use of these two instances");
+	static_assert(FMAX == 32 || ROLE == ROLE_FIRST, "only a first pass has every twiddle in GF(2^8) (kNttInstances)");
 	constexpr int EARLY = early_u_words(ROLE, FMAX);
 	const BsPass& ps = P.p;
 	const int tid = threadIdx.x;
@@ -421,9 +421,7 @@ __global__ __launch_bounds__(64 * L, 2) void antt_bs_pass(BsParams P) {
 // 8 waves (4 limbs x 2 halves): two waves per SIMD. Same tiles, tables, HBM layouts and results as
 // antt_bs_pass.
 // ------------------------------------------------------------------------------------
-constexpr int kSplitNT = 512;  // 8 waves
 #define BS3_SB() __builtin_amdgcn_sched_barrier(0)
-static size_t split_lds_bytes() { return ((size_t)8 * kPlane + (size_t)kMaxStages) * sizeof(uint32_t); }
 
 template <int ROLE>
 __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
@@ -573,106 +571,23 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 }
 
 // ------------------------------------------------------------------------------------
-// host: kernel selection and launch (the pass tables come from antt_passes.cpp)
+// host: the instances of the two families and their launch (the pass tables and the choice of a
+// kernel come from antt_passes.cpp)
 // ------------------------------------------------------------------------------------
-// kernel instance per (limbs, role, largest stage field)
-template <int L, int FMAX>
-static const void* kernel_for_f(int role) {
-	static const void* const by_role[4] = {(const void*)antt_bs_pass<L, ROLE_FIRST, FMAX>, (const void*)antt_bs_pass<L, ROLE_MID, FMAX>,
-	                                       (const void*)antt_bs_pass<L, ROLE_LAST, FMAX>, (const void*)antt_bs_pass<L, ROLE_SINGLE, FMAX>};
-	return by_role[role];
-}
-static const void* kernel_for(int L, int role, int fmax) {
-	if (L == 4) return fmax <= 8 ? kernel_for_f<4, 8>(role) : kernel_for_f<4, 32>(role);
-	return fmax <= 8 ? kernel_for_f<1, 8>(role) : kernel_for_f<1, 32>(role);
-}
-
-// lane-split kernels: upper passes only (use_split)
-static const void* split_kernel_for(int role) {
-	return role == ROLE_FIRST ? (const void*)antt_bs3_pass<ROLE_FIRST> : (const void*)antt_bs3_pass<ROLE_MID>;
-}
-
-int bs_prepare(bn_antt_plan* plan) {
-	for (int L : {1, 4})
-		for (int role = 0; role < 4; role++)
-			for (int f : {8, 32})
-				BN_HIP(hipFuncSetAttribute(kernel_for(L, role, f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds_bytes(L)));
-	for (int role : {ROLE_FIRST, ROLE_MID})
-		BN_HIP(hipFuncSetAttribute(split_kernel_for(role), hipFuncAttributeMaxDynamicSharedMemorySize, (int)split_lds_bytes()));
-	// the pass tables are built here, once per plan, so that a table the kernels cannot run (a bottom
-	// tile that is not one contiguous run, stage bits that are not the top tile bits) fails the plan
-	// and never reaches a launch
-	int rc = plan_pass_tables(plan->log_h, plan->log_rate, plan->s_host, plan->passes, plan->rt);
-	if (rc != BN_OK) return rc;
-	rc = rr_prepare(plan);
-	if (rc != BN_OK) return rc;
-	int cus = 0;
-	BN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, plan->device));
-	plan->num_cus = std::max(cus, 1);
-	plan->variant = 5;  // mixed: register tiles for GF(2^8)-only passes, LDS tiles for the others
-	return BN_OK;
-}
-
-// The environment switches of the development build (make BN_DEV=1), all of them. The product
-// build reads none. They measure or select among kernels the product itself launches:
-//   BN_DEBUG_FLAGS=bits  skip work for timing (wrong results): 1 no tile loads, 2 no tile stores,
-//                        4 no multiplies (antt_bs_pass; antt_rr_pass takes bits 1 and 2, antt_bs3_pass bit 2)
-//   BN_TRACE=1           per-wave phase times in cycles on stderr (antt_bs_pass, antt_bs3_pass)
-//   BN_SPLIT=0/1         upper GF(2^16/32) passes never / always on the lane-split kernel
-//   BN_RR_LAST=0         small bottom passes stay on LDS tiles
-//   BN_ANTT_VARIANT=v    kernel variant of new plans (antt.hip)
-static BsDevKnobs dev_knobs() {
-	BsDevKnobs k;
-#ifdef BN_DEV
-	if (const char* e = getenv("BN_DEBUG_FLAGS")) k.dbg = atoi(e) & 7;
-	if (const char* e = getenv("BN_SPLIT")) k.split = atoi(e);
-	if (const char* e = getenv("BN_RR_LAST")) k.rr_last = atoi(e);
-	k.trace = getenv("BN_TRACE") != nullptr;
-#endif
-	return k;
-}
-
-// GF(2^16/32) LDS-tile upper passes of a small launch (one 2^20 transform) run
-// lane-split (antt_bs3_pass: two waves per product, two waves per SIMD instead of one). 2^20 A/B
-// (EXPERIMENTS.md section 5.1, round 4): upper GF(2^32) pass 0.0139 vs 0.0158 ms, bottom pass 0.0514 vs 0.0496 ms,
-// so the bottom pass keeps one wave per limb and has no lane-split kernel
-static bool use_split(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
-	if (plan->limbs != 4 || pass_fmax(pass) <= 8) return false;
-	if (pass.role == ROLE_LAST || pass.role == ROLE_SINGLE) return false;
-	if (kn.split >= 0) return kn.split != 0;
-	return small_launch(plan, ntiles);
-}
-
-// Bottom pass of a small launch (one wave per SIMD either way) on
-// register tiles, compiled without the three-waves bound (antt_rr.hip rr_pass_kernel): C3 (one 2^20
-// transform) 0.0800-0.0802 vs 0.0822-0.0824 ms on LDS tiles (round 5, EXPERIMENTS.md section 5.1).
-static bool use_rr_last(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
-	if (kn.rr_last == 0 || plan->variant != 5 || plan->limbs != 4 || pass.role != ROLE_LAST) return false;
-	return small_launch(plan, ntiles);
-}
-
-// What runs a pass of `ntiles` tiles (one workgroup per tile). The only place that decides it:
-// launch_one launches what this returns and bs_pass_kernel reports it.
-struct BsSel {
-	const void* kernel;  // nullptr: the plan's variant has no bitsliced passes
-	bool rr;             // a register-tile kernel: rr_launch_pass launches it (RrParams, its own geometry)
-	unsigned threads;    // otherwise: workgroup size and dynamic LDS of a BsParams kernel of this file
-	size_t lds;
+template <int I>
+struct BsAt {
+	static const void* fn() {
+		constexpr NttInstance k = kNttInstances[I];
+		if constexpr (k.family == NttFamily::Bs) return (const void*)antt_bs_pass<k.limbs, k.role, k.fmax>;
+		else if constexpr (k.family == NttFamily::Bs3) return (const void*)antt_bs3_pass<k.role>;
+		else return nullptr;
+	}
 };
-static BsSel select_pass(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles, const BsDevKnobs& kn) {
-	const int L = plan->limbs, fmax = pass_fmax(pass);
-	// variant 4: every pass on register tiles; variant 5 (mixed): register tiles for the passes whose
-	// twiddles all lie in GF(2^8) (their kernel fits four waves per SIMD), LDS tiles for the others
-	if (plan->variant == 4 || (plan->variant == 5 && fmax <= 8) || use_rr_last(plan, pass, ntiles, kn))
-		return {rr_pass_kernel(plan, pass, ntiles), true, 0, 0};
-	if (plan->variant != 1 && plan->variant != 5) return {nullptr, false, 0, 0};
-	if (use_split(plan, pass, ntiles, kn)) return {split_kernel_for(pass.role), false, kSplitNT, split_lds_bytes()};
-	return {kernel_for(L, pass.role, fmax), false, 64u * (unsigned)L, tile_lds_bytes(L)};
-}
+const void* bs_kernel_fn(int instance) { return instance_table<BsAt>(instance, std::make_index_sequence<kNttInstanceCount>()); }
 
 // BN_TRACE: the phase cycles the waves of one launch left in d_trace (8 words per wave, the slots of
 // tr[] in antt_bs_pass), as averages per wave-tile
-static int print_trace(int i, const BsSel& sel, int fmax, const unsigned long long* d_trace, size_t waves, hipStream_t st) {
+static int print_trace(int i, const NttLaunch& nl, int fmax, const unsigned long long* d_trace, size_t waves, hipStream_t st) {
 	std::vector<unsigned long long> h(waves * 8);
 	BN_HIP(hipStreamSynchronize(st));
 	BN_HIP(hipMemcpy(h.data(), d_trace, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost));
@@ -683,7 +598,7 @@ static int print_trace(int i, const BsSel& sel, int fmax, const unsigned long lo
 	fprintf(stderr,
 	        "trace pass %d (%s, fmax %d, %zu wave-tiles, cycles per wave-tile): load %.0f  block %.0f [pre %.0f mul %.0f post %.0f]  "
 	        "inword+tr %.0f  store %.0f\n",
-	        i, sel.threads == kSplitNT ? "split" : "tile", fmax, (size_t)acc[4], acc[0] / t, acc[1] / t, acc[5] / t, acc[6] / t,
+	        i, nl.threads == kSplitNT ? "split" : "tile", fmax, (size_t)acc[4], acc[0] / t, acc[1] / t, acc[5] / t, acc[6] / t,
 	        acc[7] / t, acc[2] / t, acc[3] / t);
 	return BN_OK;
 }
@@ -691,10 +606,9 @@ static int print_trace(int i, const BsSel& sel, int fmax, const unsigned long lo
 static int launch_one(bn_antt_plan* plan, int i, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st,
                       const BsDevKnobs& kn) {
 	const BsPass& pass = plan->passes[i];
-	const size_t ntiles = (batch << plan->log_rate) << pass.n_outer;
-	const BsSel sel = select_pass(plan, pass, ntiles, kn);
-	if (sel.rr) return rr_launch_pass(plan, i, plan->rt[i], sel.kernel, ntiles, kn, d_in, d_out, st);
-	if (!sel.kernel) BN_FAIL(BN_ERR_UNSUPPORTED, "variant %d has no bitsliced passes", plan->variant);
+	const NttLaunch nl = plan_pass(plan, pass, false, batch, kn);
+	if (nl.instance < 0) BN_FAIL(BN_ERR_UNSUPPORTED, "variant %d has no bitsliced passes", plan->variant);
+	if (kNttInstances[nl.instance].family == NttFamily::Rr) return rr_launch_pass(plan, i, nl, kn, d_in, d_out, st);
 	BsParams prm;
 	prm.src = d_in;
 	prm.dst = d_out;
@@ -703,7 +617,7 @@ static int launch_one(bn_antt_plan* plan, int i, const uint32_t* d_in, uint32_t*
 	prm.dbg = kn.dbg;
 	prm.p = pass;
 	prm.trace = nullptr;
-	const size_t waves = ntiles * (sel.threads / 64);
+	const size_t waves = nl.grid * (nl.threads / 64);
 	if (kn.trace) {
 		constexpr size_t kTraceBytes = (size_t)1 << 26;
 		static unsigned long long* trbuf = nullptr;
@@ -716,10 +630,10 @@ static int launch_one(bn_antt_plan* plan, int i, const uint32_t* d_in, uint32_t*
 	int rc = timing_begin(plan, i, st);
 	if (rc != BN_OK) return rc;
 	void* args[] = {&prm};
-	BN_HIP(hipLaunchKernel(sel.kernel, dim3((unsigned)ntiles), dim3(sel.threads), args, sel.lds, st));
+	BN_HIP(hipLaunchKernel(bs_kernel_fn(nl.instance), dim3((unsigned)nl.grid), dim3(nl.threads), args, nl.lds, st));
 	rc = timing_end(plan, i, st);
 	if (rc != BN_OK || !prm.trace) return rc;
-	return print_trace(i, sel, pass_fmax(pass), prm.trace, waves, st);
+	return print_trace(i, nl, pass_fmax(pass), prm.trace, waves, st);
 }
 
 // the kernel pass i launches under the plan's variant (variants 1, 4, 5), nullptr otherwise
@@ -727,13 +641,12 @@ const void* bs_pass_kernel(bn_antt_plan* plan, int i) {
 	if (i < 0 || (size_t)i >= plan->passes.size()) return nullptr;
 	// the kernel for ONE transform (bench / profiles): a batched launch of the same pass may pick
 	// another (the lane-split and small-bottom kernels depend on the tile count)
-	const BsPass& pass = plan->passes[i];
-	const size_t ntiles = ((size_t)1 << plan->log_rate) << pass.n_outer;
-	return select_pass(plan, pass, ntiles, dev_knobs()).kernel;
+	const NttLaunch nl = plan_pass(plan, plan->passes[i], false, 1, bs_dev_knobs());
+	return nl.instance < 0 ? nullptr : ntt_kernel_fn(nl.instance);
 }
 
 int launch_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st) {
-	const BsDevKnobs kn = dev_knobs();
+	const BsDevKnobs kn = bs_dev_knobs();
 	for (size_t i = 0; i < plan->passes.size(); i++) {
 		int rc = launch_one(plan, (int)i, d_in, d_out, batch, st, kn);
 		if (rc != BN_OK) return rc;
@@ -748,7 +661,7 @@ int launch_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t 
 int bs_time_passes(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, int reps,
                    hipStream_t st, float* ms, int max_passes, int* n_out) {
 	const int n_passes = (int)plan->passes.size();
-	BsDevKnobs kn = dev_knobs();
+	BsDevKnobs kn = bs_dev_knobs();
 	kn.trace = false;
 	const int saved = plan->timing;
 	plan->timing = 0;

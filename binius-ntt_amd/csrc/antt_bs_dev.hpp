@@ -31,14 +31,8 @@ __device__ __forceinline__ void mul_tw(int field, const uint32_t* x, const uint3
 	}
 }
 
-// LDS image of a tile: one plane per limb, block q of limb l at l*kPlane + q*kLimbStride (stride 36
-// words: 16 consecutive blocks of one plane hit 16 distinct 4-bank groups, so a wave's
-// ds_read_b128 over consecutive blocks is conflict-free).
-constexpr int kPlane = kTileBlocks * kLimbStride;
+// (the LDS image of a tile, kPlane, and the kernels' LDS sizes: antt_passes.hpp)
 constexpr int kLoads = kTileBlocks * 8 / 64;  // 16-byte global loads per lane per tile
-// LDS of a one-wave-per-limb tile kernel (antt_bs_pass, antt_inv_bs_pass): the tile + one word per
-// stage and wave for the workgroup-uniform twiddle parts
-constexpr size_t tile_lds_bytes(int L) { return ((size_t)L * kPlane + (size_t)L * kMaxStages) * sizeof(uint32_t); }
 
 // Words of a block stage's U that a lane requests from LDS next to V, ahead of the multiply circuit, so
 // that their latency runs under it; the other words are read after the circuit. All 32 with the

@@ -43,6 +43,7 @@ __global__ __launch_bounds__(64 * L, 2) void antt_inv_bs_pass(InvBsParams P) {
 	constexpr int NT = 64 * L;
 	constexpr bool IN_COMPACT = ROLE == ROLE_FIRST || ROLE == ROLE_SINGLE;  // bottom pass
 	constexpr bool OUT_COMPACT = ROLE == ROLE_LAST || ROLE == ROLE_SINGLE;
+	static_assert(FMAX == 32 || (FMAX == 8 && ROLE == ROLE_LAST), "only the top pass has every twiddle in GF(2^8) (kNttInstances)");
 	const BsPass& ps = P.p;
 	const int tid = threadIdx.x;
 	// wave w owns limb w of the tile for every stage (as antt_bs_pass)
@@ -191,44 +192,32 @@ __global__ __launch_bounds__(64 * L, 2) void antt_inv_bs_pass(InvBsParams P) {
 	}
 }
 
-template <int L, int FMAX>
-static const void* inv_kernel_for_f(int role) {
-	static const void* const by_role[4] = {
-	    (const void*)antt_inv_bs_pass<L, ROLE_FIRST, FMAX>, (const void*)antt_inv_bs_pass<L, ROLE_MID, FMAX>,
-	    (const void*)antt_inv_bs_pass<L, ROLE_LAST, FMAX>, (const void*)antt_inv_bs_pass<L, ROLE_SINGLE, FMAX>};
-	return by_role[role];
-}
-static const void* inv_kernel_for(int L, int role, int fmax) {
-	if (L == 4) return fmax <= 8 ? inv_kernel_for_f<4, 8>(role) : inv_kernel_for_f<4, 32>(role);
-	return fmax <= 8 ? inv_kernel_for_f<1, 8>(role) : inv_kernel_for_f<1, 32>(role);
-}
+template <int I>
+struct InvAt {
+	static const void* fn() {
+		constexpr NttInstance k = kNttInstances[I];
+		if constexpr (k.family == NttFamily::InvBs) return (const void*)antt_inv_bs_pass<k.limbs, k.role, k.fmax>;
+		return nullptr;
+	}
+};
+const void* inv_kernel_fn(int instance) { return instance_table<InvAt>(instance, std::make_index_sequence<kNttInstanceCount>()); }
 
 int launch_inv_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, int coset, size_t batch, hipStream_t st) {
 	const std::vector<BsPass>& passes = plan->passes;
-	const size_t n_passes = passes.size();
-	const int L = plan->limbs;
-	if (!plan->inv_prepared) {
-		for (int role = 0; role < 4; role++)
-			for (int f : {8, 32})
-				BN_HIP(hipFuncSetAttribute(inv_kernel_for(L, role, f), hipFuncAttributeMaxDynamicSharedMemorySize,
-				                           (int)tile_lds_bytes(L)));
-		plan->inv_prepared = 1;
-	}
+	const BsDevKnobs kn;  // no development switch touches the inverse
 	// the forward passes run top stages first and the bottom pass last: the inverse takes them in
 	// reverse, so the bottom pass is its first (compact in) and forward pass 0 its last (compact out)
-	for (size_t i = n_passes; i-- > 0;) {
+	for (size_t i = passes.size(); i-- > 0;) {
+		const NttLaunch nl = plan_pass(plan, passes[i], true, batch, kn);
+		if (nl.instance < 0) BN_FAIL(BN_ERR_UNSUPPORTED, "variant %d has no bitsliced passes", plan->variant);
 		InvBsParams prm;
 		prm.src = d_in;
 		prm.dst = d_out;
 		prm.log_h = plan->log_h;
 		prm.coset = coset;
 		prm.p = passes[i];
-		const bool first = i + 1 == n_passes, last = i == 0;
-		const int role = first && last ? ROLE_SINGLE : first ? ROLE_FIRST : last ? ROLE_LAST : ROLE_MID;
-		const size_t ntiles = batch << passes[i].n_outer;
 		void* args[] = {&prm};
-		BN_HIP(hipLaunchKernel(inv_kernel_for(L, role, pass_fmax(passes[i])), dim3((unsigned)ntiles), dim3(64 * L), args,
-		                       tile_lds_bytes(L), st));
+		BN_HIP(hipLaunchKernel(inv_kernel_fn(nl.instance), dim3((unsigned)nl.grid), dim3(nl.threads), args, nl.lds, st));
 	}
 	return BN_OK;
 }

@@ -1,9 +1,11 @@
 // Host-side planning of the additive NTT: the subspace table, the split of a transform into passes,
 // the pass tables of the LDS-tile kernels (BsPass, antt_bs.hip / antt_inv.hip) and of the register-tile
-// kernels (RtPass, antt_rr.hip), and the two host-only exports that show those tables to the tests.
+// kernels (RtPass, antt_rr.hip), the choice of a kernel instance per launch (ntt_plan_launch), and the
+// two host-only exports that show the tables to the tests.
 // Integer code on (log_h, log_rate, subspace table): no device, no plan.
 #include "antt_passes.hpp"
 
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -222,6 +224,48 @@ int plan_pass_tables(int log_h, int log_rate, const std::vector<uint32_t>& s, st
 		if (!make_rt(passes[i], bottom, &rt[i])) BN_FAIL(BN_ERR_UNSUPPORTED, "register-tile pass table: stage bits are not the top tile bits");
 	}
 	return BN_OK;
+}
+
+BsDevKnobs bs_dev_knobs() {
+	BsDevKnobs k;
+#ifdef BN_DEV
+	if (const char* e = getenv("BN_DEBUG_FLAGS")) k.dbg = atoi(e) & 7;
+	if (const char* e = getenv("BN_SPLIT")) k.split = atoi(e);
+	if (const char* e = getenv("BN_RR_LAST")) k.rr_last = atoi(e);
+	if (const char* e = getenv("BN_ANTT_VARIANT"))
+		if (const int v = atoi(e); v != 0 && valid_variant(v)) k.variant = v;
+	k.trace = getenv("BN_TRACE") != nullptr;
+#endif
+	return k;
+}
+
+NttLaunch ntt_plan_launch(int limbs, int variant, bool inverse, int role, int fmax, size_t ntiles, int num_cus,
+                          const BsDevKnobs& kn) {
+	// fewer tiles than two per CU run at most one wave per SIMD, and take the kernels built for that
+	const bool small = ntiles < (size_t)2 * (size_t)num_cus;
+	const bool bottom = role == ROLE_LAST || role == ROLE_SINGLE;
+	const int f8_32 = fmax <= 8 ? 8 : 32;
+	// small bottom pass on register tiles without the three-waves bound: C3 0.0800-0.0802 vs 0.0822-0.0824 ms
+	const bool rr_last = variant == 5 && limbs == 4 && role == ROLE_LAST && small && kn.rr_last != 0;
+	// GF(2^16/32) LDS-tile upper passes of a small launch run lane-split (two waves per SIMD instead of
+	// one): upper GF(2^32) pass 0.0139 vs 0.0158 ms, bottom pass 0.0514 vs 0.0496 ms, so not the bottom
+	const bool split = limbs == 4 && fmax > 8 && !bottom && (kn.split >= 0 ? kn.split != 0 : small);
+	if (variant != 1 && variant != 4 && variant != 5) return {-1, ntiles, 0, 0u};
+	NttInstance k;
+	if (inverse)  // the forward's passes in reverse: its first pass is the inverse's last
+		k = {NttFamily::InvBs, limbs, role == ROLE_FIRST ? ROLE_LAST : role == ROLE_LAST ? ROLE_FIRST : role, f8_32, 0};
+	else if (variant == 4 || (variant == 5 && fmax <= 8) || rr_last)
+		k = {NttFamily::Rr, limbs, role, fmax <= 8 ? 8 : fmax <= 16 ? 16 : 32, limbs == 4 && role == ROLE_LAST && small ? 1 : bottom ? 3 : 1};
+	else if (split)
+		k = {NttFamily::Bs3, 4, role, 0, 0};
+	else
+		k = {NttFamily::Bs, limbs, role, f8_32, 0};
+	NttLaunch l{-1, ntiles, instance_lds_bytes(k), instance_threads(k)};
+	for (int i = 0; i < kNttInstanceCount && l.instance < 0; i++) {
+		const NttInstance& c = kNttInstances[i];
+		if (c.family == k.family && c.limbs == k.limbs && c.role == k.role && c.fmax == k.fmax && c.occ == k.occ) l.instance = i;
+	}
+	return l;
 }
 
 // the tables of (log_h, log_rate) without a plan, for the host-only exports

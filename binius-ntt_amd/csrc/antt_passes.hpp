@@ -1,7 +1,9 @@
-// Pass planning of the bitsliced additive NTT (host only, antt_passes.cpp): tile constants, the pass
-// tables the kernels take as arguments, and the planner that builds them from the subspace table.
+// Pass planning of the bitsliced additive NTT (host only, antt_passes.cpp): tile and LDS constants,
+// the pass tables the kernels take as arguments, the planner that builds them from the subspace
+// table, the list of pass-kernel instances, and the planner that picks one of them per launch.
 // Tiles of 128 bitsliced 32-element blocks, host-tabulated twiddle contributions. No HIP header: the
-// planner is integer code, and the device side (antt_bs_dev.hpp) includes this file for the tables.
+// planners are integer code, and the device side (antt_bs_dev.hpp) includes this file for the tables,
+// the constants and the instance list.
 #pragma once
 
 #include <stddef.h>
@@ -20,6 +22,22 @@ constexpr int kMaxOuter = 32 - 5 - kBlkBits;
 constexpr int kMaxRateBits = 8;
 
 enum { ROLE_FIRST = 0, ROLE_MID = 1, ROLE_LAST = 2, ROLE_SINGLE = 3 };
+
+// LDS image of a tile: one plane per limb, block q of limb l at l*kPlane + q*kLimbStride (stride 36
+// words: 16 consecutive blocks of one plane hit 16 distinct 4-bank groups, so a wave's
+// ds_read_b128 over consecutive blocks is conflict-free).
+constexpr int kPlane = kTileBlocks * kLimbStride;
+// LDS of a one-wave-per-limb tile kernel (antt_bs_pass, antt_inv_bs_pass): the tile + one word per
+// stage and wave for the workgroup-uniform twiddle parts
+constexpr size_t tile_lds_bytes(int L) { return ((size_t)L * kPlane + (size_t)L * kMaxStages) * sizeof(uint32_t); }
+// the lane-split kernel (antt_bs3_pass): 8 waves, the tile double-buffered + one word per stage
+constexpr int kSplitNT = 512;
+constexpr size_t kSplitLdsBytes = ((size_t)8 * kPlane + (size_t)kMaxStages) * sizeof(uint32_t);
+namespace rr {  // antt_rr_pass stages half a tile through LDS: compact elements or coalesced bitsliced lines
+constexpr int kSlot = 36;                // LDS words per staged block (32 + 4 pad: conflict-free b128 writes)
+constexpr int kStagePlane = 64 * kSlot;  // one limb plane of a half tile
+constexpr size_t lds_bytes(int L) { return (size_t)L * kStagePlane * sizeof(uint32_t); }
+}  // namespace rr
 
 // bit masks of the bit-lanes p with bit j of p set (constexpr: callable from device code as it is)
 constexpr uint32_t lane_mask(int j) {
@@ -78,5 +96,78 @@ int pass_fmax(const BsPass& p);
 // run its kernels address, or a pass's stage bits are not the top tile bits.
 int plan_pass_tables(int log_h, int log_rate, const std::vector<uint32_t>& s, std::vector<BsPass>& passes,
                      std::vector<RtPass>& rt);
+
+// ---- which kernel runs a launch. A family is one kernel template and the params struct it takes:
+// antt_bs_pass, antt_bs3_pass (BsParams), antt_inv_bs_pass (InvBsParams), antt_rr_pass (RrParams)
+enum class NttFamily { Bs, Bs3, InvBs, Rr };
+// One instance: the family's template arguments (fmax 0: antt_bs3_pass<ROLE>; occ: antt_rr_pass only)
+struct NttInstance {
+	NttFamily family;
+	int limbs, role, fmax, occ;
+};
+// Every pass kernel of the library: the .hip files instantiate from this list and nothing else, the
+// plan sets the LDS attribute of each entry, and ntt_plan_launch returns an index into it. A plan
+// holds FIRST at fmax 8 / 16 / 32, MID and LAST at 16 / 32, SINGLE at 16 (DESIGN.md section 5.1;
+// tests/cpp/test_host_asan.cpp sweeps every plan). The LDS-tile kernels run fmax 16 on their GF(2^32)
+// form; the inverse's roles are in its own order (its FIRST is the bottom pass).
+constexpr NttInstance kNttInstances[] = {
+    {NttFamily::Bs, 1, ROLE_FIRST, 8, 0},     {NttFamily::Bs, 4, ROLE_FIRST, 8, 0},
+    {NttFamily::Bs, 1, ROLE_FIRST, 32, 0},    {NttFamily::Bs, 4, ROLE_FIRST, 32, 0},
+    {NttFamily::Bs, 1, ROLE_MID, 32, 0},      {NttFamily::Bs, 4, ROLE_MID, 32, 0},
+    {NttFamily::Bs, 1, ROLE_LAST, 32, 0},     {NttFamily::Bs, 4, ROLE_LAST, 32, 0},
+    {NttFamily::Bs, 1, ROLE_SINGLE, 32, 0},   {NttFamily::Bs, 4, ROLE_SINGLE, 32, 0},
+    {NttFamily::Bs3, 4, ROLE_FIRST, 0, 0},    {NttFamily::Bs3, 4, ROLE_MID, 0, 0},
+    {NttFamily::InvBs, 1, ROLE_LAST, 8, 0},   {NttFamily::InvBs, 4, ROLE_LAST, 8, 0},
+    {NttFamily::InvBs, 1, ROLE_LAST, 32, 0},  {NttFamily::InvBs, 4, ROLE_LAST, 32, 0},
+    {NttFamily::InvBs, 1, ROLE_MID, 32, 0},   {NttFamily::InvBs, 4, ROLE_MID, 32, 0},
+    {NttFamily::InvBs, 1, ROLE_FIRST, 32, 0}, {NttFamily::InvBs, 4, ROLE_FIRST, 32, 0},
+    {NttFamily::InvBs, 1, ROLE_SINGLE, 32, 0}, {NttFamily::InvBs, 4, ROLE_SINGLE, 32, 0},
+    {NttFamily::Rr, 1, ROLE_FIRST, 8, 1},     {NttFamily::Rr, 4, ROLE_FIRST, 8, 1},
+    {NttFamily::Rr, 1, ROLE_FIRST, 16, 1},    {NttFamily::Rr, 4, ROLE_FIRST, 16, 1},
+    {NttFamily::Rr, 1, ROLE_FIRST, 32, 1},    {NttFamily::Rr, 4, ROLE_FIRST, 32, 1},
+    {NttFamily::Rr, 1, ROLE_MID, 16, 1},      {NttFamily::Rr, 4, ROLE_MID, 16, 1},
+    {NttFamily::Rr, 1, ROLE_MID, 32, 1},      {NttFamily::Rr, 4, ROLE_MID, 32, 1},
+    {NttFamily::Rr, 1, ROLE_LAST, 16, 3},     {NttFamily::Rr, 4, ROLE_LAST, 16, 3},
+    {NttFamily::Rr, 1, ROLE_LAST, 32, 3},     {NttFamily::Rr, 4, ROLE_LAST, 32, 3},
+    {NttFamily::Rr, 1, ROLE_SINGLE, 16, 3},   {NttFamily::Rr, 4, ROLE_SINGLE, 16, 3},
+    // the bottom pass without the three-waves bound (no spills), for small launches
+    {NttFamily::Rr, 4, ROLE_LAST, 16, 1},     {NttFamily::Rr, 4, ROLE_LAST, 32, 1},
+};
+constexpr int kNttInstanceCount = (int)(sizeof(kNttInstances) / sizeof(kNttInstances[0]));
+// workgroup size and dynamic LDS bytes of an instance: its family's
+constexpr unsigned instance_threads(const NttInstance& k) { return k.family == NttFamily::Bs3 ? kSplitNT : 64u * (unsigned)k.limbs; }
+constexpr size_t instance_lds_bytes(const NttInstance& k) {
+	return k.family == NttFamily::Rr ? rr::lds_bytes(k.limbs) : k.family == NttFamily::Bs3 ? kSplitLdsBytes : tile_lds_bytes(k.limbs);
+}
+
+// Kernel variants: 0 compact tiles (log_h < 12), 1 bitsliced LDS tiles (antt_bs_pass), 4 bitsliced
+// register tiles (antt_rr_pass), 5 = 4 for the passes whose twiddles all lie in GF(2^8) (their kernel
+// fits four waves per SIMD) and 1 for the others (the default for log_h >= 12).
+constexpr bool valid_variant(int v) { return v == 0 || v == 1 || v == 4 || v == 5; }
+
+// The environment switches of the development build (make BN_DEV=1), all of them; the product build
+// reads none and has the defaults. They measure or select among kernels the product itself launches:
+//   BN_DEBUG_FLAGS=bits  skip work for timing (wrong results): 1 no tile loads, 2 no tile stores,
+//                        4 no multiplies (antt_bs_pass; antt_rr_pass takes bits 1 and 2, antt_bs3_pass bit 2)
+//   BN_TRACE=1           per-wave phase times in cycles on stderr (antt_bs_pass, antt_bs3_pass)
+//   BN_SPLIT=0/1         upper GF(2^16/32) passes never / always on the lane-split kernel
+//   BN_RR_LAST=0         small bottom passes stay on LDS tiles
+//   BN_ANTT_VARIANT=v    kernel variant of new plans with log_h >= 12 (1, 4 or 5)
+struct BsDevKnobs {
+	int dbg = 0, split = -1, rr_last = -1, variant = 5;
+	bool trace = false;
+};
+BsDevKnobs bs_dev_knobs();
+
+// One launch of a pass: workgroup b transforms tile b.
+struct NttLaunch {
+	int instance;  // index into kNttInstances; -1: the variant has no bitsliced passes
+	size_t grid, lds;  // tiles, dynamic LDS bytes
+	unsigned threads;
+};
+// What runs the pass of (the forward's) role `role` and largest stage field `fmax` over `ntiles` tiles
+// on a device of `num_cus` compute units. The only place that decides it.
+NttLaunch ntt_plan_launch(int limbs, int variant, bool inverse, int role, int fmax, size_t ntiles, int num_cus,
+                          const BsDevKnobs& kn);
 
 }  // namespace bn

@@ -24,7 +24,6 @@ struct bn_antt_plan {
 	// filled once by bs_prepare; empty for variant-0 plans
 	std::vector<bn::BsPass> passes;
 	std::vector<bn::RtPass> rt;
-	int inv_prepared = 0;  // LDS attribute of the bitsliced inverse kernels set (antt_inv.hip)
 	hipStream_t own_stream = nullptr;
 	// host-apply staging
 	void* h_dev_in = nullptr;

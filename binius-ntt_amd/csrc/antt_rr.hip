@@ -21,11 +21,7 @@
 // the others (coalesced 1 KiB per wave-instruction, re-read lane-private). VGPRs set the occupancy.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdio>
-#include <cstring>
 #include <type_traits>
-#include <vector>
 
 #include "antt_bs.hpp"
 #include "antt_bs_dev.hpp"
@@ -33,14 +29,6 @@
 
 namespace bn {
 namespace rr {
-
-// minimum waves per SIMD the compiler must fit (VGPR budget 512 / n): the bottom pass needs 170
-// registers unconstrained and fits 168 (three waves) without spills; the upper passes are left
-// unconstrained (114-164 registers, three or four waves: forcing three made the scheduler spill)
-template <int ROLE>
-struct RrOcc {
-	static constexpr int value = (ROLE == ROLE_LAST || ROLE == ROLE_SINGLE) ? 3 : 1;
-};
 
 struct RrParams {
 	const uint32_t* src;
@@ -57,9 +45,6 @@ struct RrParams {
 #else
 #define RR_DBG(P) 0
 #endif
-
-constexpr int kSlot = 36;                 // LDS words per staged block (32 + 4 pad: conflict-free b128 writes)
-constexpr int kStagePlane = 64 * kSlot;   // one limb plane of a half tile
 
 // ld_stream / st_stream on four consecutive registers
 __device__ __forceinline__ void ld4(const uint32_t* p, uint32_t* r) {
@@ -111,12 +96,18 @@ __device__ __forceinline__ void fma_tw(int field, uint32_t tw, const uint32_t* v
 	}
 }
 
-template <int L, int ROLE, int FMAX, int OCC = RrOcc<ROLE>::value>
+// OCC: minimum waves per SIMD the compiler must fit (VGPR budget 512 / n). The bottom pass needs 170
+// registers unconstrained and takes 3 (168, with spills at some instances); small launches take its
+// instances with 1 (no spills). The upper passes are left unconstrained (114-164 registers, three or
+// four waves: forcing three made the scheduler spill)
+template <int L, int ROLE, int FMAX, int OCC>
 __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 	extern __shared__ uint32_t lds[];
 	constexpr bool IN_COMPACT = ROLE == ROLE_FIRST || ROLE == ROLE_SINGLE;
 	constexpr bool LAST = ROLE == ROLE_LAST || ROLE == ROLE_SINGLE;
 	constexpr int NT = 64 * L;
+	static_assert(FMAX > 8 || ROLE == ROLE_FIRST, "only a first pass has every twiddle in GF(2^8) (kNttInstances)");
+	static_assert(ROLE != ROLE_SINGLE || FMAX == 16, "a single pass is log_h 12: its twiddles lie in GF(2^16)");
 	// the upper passes whose twiddles all lie in GF(2^8) run each block stage with the circuit of its
 	// class 0 / 2 / 4 / 8; the bottom pass and the FMAX 16 / 32 instances round the small classes up to 8
 	constexpr bool SMALL = FMAX <= 8 && !LAST;
@@ -299,11 +290,7 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 				// register allocator copy R0/R1 at their merge)
 				uint32_t W[32];
 				__builtin_amdgcn_sched_barrier(0);
-				if (FMAX <= 8) {
-#pragma unroll
-					for (int i = 0; i < 8; i++) W[i] = ps.pat[s][i] ^ (uint32_t)__builtin_amdgcn_sbfe(cb, i, 1);
-					bsm3x4_mul_acc(R1, W, R0);
-				} else if (FMAX <= 16) {
+				if (FMAX <= 16) {  // (no bottom pass lies in GF(2^8))
 #pragma unroll
 					for (int i = 0; i < 16; i++) W[i] = ps.pat[s][i] ^ (uint32_t)__builtin_amdgcn_sbfe(cb, i, 1);
 					bsm4x2_mul_acc(R1, W, R0);
@@ -373,64 +360,37 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 	}
 }
 
-template <int L, int FMAX>
-static const void* kernel_f(int role) {
-	static const void* const by_role[4] = {(const void*)antt_rr_pass<L, ROLE_FIRST, FMAX>, (const void*)antt_rr_pass<L, ROLE_MID, FMAX>,
-	                                       (const void*)antt_rr_pass<L, ROLE_LAST, FMAX>, (const void*)antt_rr_pass<L, ROLE_SINGLE, FMAX>};
-	return by_role[role];
-}
-static const void* kernel_for(int L, int role, int fmax) {
-	if (L == 4) return fmax <= 8 ? kernel_f<4, 8>(role) : fmax <= 16 ? kernel_f<4, 16>(role) : kernel_f<4, 32>(role);
-	return fmax <= 8 ? kernel_f<1, 8>(role) : fmax <= 16 ? kernel_f<1, 16>(role) : kernel_f<1, 32>(role);
-}
-// the bottom pass without the three-waves bound: no spills (see rr_pass_kernel)
-static const void* kernel_small_last(int fmax) {
-	return fmax <= 8 ? (const void*)antt_rr_pass<4, ROLE_LAST, 8, 1> : fmax <= 16 ? (const void*)antt_rr_pass<4, ROLE_LAST, 16, 1>
-	                                                                              : (const void*)antt_rr_pass<4, ROLE_LAST, 32, 1>;
-}
-// every role stages through LDS: compact elements (first / last pass) or coalesced bitsliced lines
-static size_t lds_bytes(int L) { return (size_t)L * kStagePlane * sizeof(uint32_t); }
+template <int I>
+struct RrAt {
+	static const void* fn() {
+		constexpr NttInstance k = kNttInstances[I];
+		if constexpr (k.family == NttFamily::Rr) return (const void*)antt_rr_pass<k.limbs, k.role, k.fmax, k.occ>;
+		return nullptr;
+	}
+};
 
 }  // namespace rr
 
-int rr_prepare(bn_antt_plan* plan) {
-	(void)plan;
-	for (int L : {1, 4})
-		for (int role = 0; role < 4; role++)
-			for (int f : {8, 16, 32})
-				BN_HIP(hipFuncSetAttribute(rr::kernel_for(L, role, f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rr::lds_bytes(L)));
-	for (int f : {8, 16, 32})
-		BN_HIP(hipFuncSetAttribute(rr::kernel_small_last(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rr::lds_bytes(4)));
-	return BN_OK;
-}
-
-// The kernel of a pass over `ntiles` tiles. The bottom pass of a small launch runs one wave per SIMD
-// whatever its register count, so it takes the instance compiled without the three-waves bound.
-const void* rr_pass_kernel(const bn_antt_plan* plan, const BsPass& pass, size_t ntiles) {
-	const int fmax = pass_fmax(pass);
-	if (plan->limbs == 4 && pass.role == ROLE_LAST && small_launch(plan, ntiles)) return rr::kernel_small_last(fmax);
-	return rr::kernel_for(plan->limbs, pass.role, fmax);
-}
+const void* rr_kernel_fn(int instance) { return instance_table<rr::RrAt>(instance, std::make_index_sequence<kNttInstanceCount>()); }
 
 // pass i of variant 4 (same pass split as variant 1, the plan's register-tile table of it)
-int rr_launch_pass(bn_antt_plan* plan, int i, const RtPass& rt, const void* kernel, size_t ntiles, const BsDevKnobs& kn,
-                   const uint32_t* d_in, uint32_t* d_out, hipStream_t st) {
+int rr_launch_pass(bn_antt_plan* plan, int i, const NttLaunch& nl, const BsDevKnobs& kn, const uint32_t* d_in, uint32_t* d_out,
+                   hipStream_t st) {
 	rr::RrParams prm;
 	prm.src = d_in;
 	prm.dst = d_out;
 	prm.log_h = plan->log_h;
 	prm.log_rate = plan->log_rate;
-	prm.p = rt;
+	prm.p = plan->rt[i];
 #ifdef BN_DEV
 	prm.dbg = kn.dbg & 3;
 #else
 	(void)kn;
 #endif
-	const int L = plan->limbs;
 	int rc = timing_begin(plan, i, st);
 	if (rc != BN_OK) return rc;
 	void* args[] = {&prm};
-	BN_HIP(hipLaunchKernel(kernel, dim3((unsigned)ntiles), dim3(64 * L), args, rr::lds_bytes(L), st));
+	BN_HIP(hipLaunchKernel(rr_kernel_fn(nl.instance), dim3((unsigned)nl.grid), dim3(nl.threads), args, nl.lds, st));
 	return timing_end(plan, i, st);
 }
 

@@ -8,9 +8,11 @@
 //     AdditiveNTTConf, BB31, QM31/interpolate_at) against the oracle;
 //   * the library's host-side code: the generated bitsliced circuits behind multiply_unrolled<H>,
 //     the packed-subfield helpers, bn_sumcheck_interpolate, the sumcheck round planner
-//     (csrc/sc_rounds.cpp) over every round shape, the buffer checks (csrc/buf_check.hpp), and the
-//     argument-checking / error paths of the C-ABI, the staged host calls among them (no device
-//     present here: they must fail cleanly with a status code and leak nothing);
+//     (csrc/sc_rounds.cpp) over every round shape, the additive NTT's launch planner
+//     (csrc/antt_passes.cpp) over every plan, variant and direction, the buffer checks
+//     (csrc/buf_check.hpp), and the argument-checking / error paths of the C-ABI, the staged host
+//     calls among them (no device present here: they must fail cleanly with a status code and leak
+//     nothing);
 //   * all 14 generated circuits of csrc/bitsliced_gen.hpp, compiled into this program, through
 //     the conformance routine of circuit_conformance.hpp with a small trial count: every alias
 //     mode, every operand in a heap allocation of exactly its documented size, so a gate that
@@ -35,6 +37,7 @@
 #include "utils/bitslicing.hpp"
 #include "utils/common.hpp"
 #include "../../oracle/oracle.h"
+#include "antt_passes.hpp"
 #include "buf_check.hpp"
 #include "circuit_conformance.hpp"
 #include "sc_rounds.hpp"
@@ -305,6 +308,135 @@ static void sumcheck_planner_checks() {
 	check(L.kernel == ScKernel::Fold0G16, "sumcheck planner: threshold overrides choose only among instantiated kernels");
 }
 
+// The additive NTT's launch planner (csrc/antt_passes.cpp, host only): every plan the bitsliced path
+// accepts, both fields, every variant, both directions, small and large launches, then the
+// hand-derived selections.
+static void ntt_planner_checks() {
+	using namespace bn;
+	constexpr int kCus = 256;
+	auto is = [](const NttLaunch& l, NttFamily f, int limbs, int role, int fmax, int occ) {
+		if (l.instance < 0 || l.instance >= kNttInstanceCount) return false;
+		const NttInstance& k = kNttInstances[l.instance];
+		return k.family == f && k.limbs == limbs && k.role == role && k.fmax == fmax && k.occ == occ;
+	};
+	check(kNttInstanceCount == 40, "NTT planner: the instance list has 40 entries");
+	check(tile_lds_bytes(1) == 18480 && tile_lds_bytes(4) == 73920 && kSplitNT == 512 && kSplitLdsBytes == 147504 &&
+	          rr::lds_bytes(1) == 9216 && rr::lds_bytes(4) == 36864,
+	      "NTT planner: LDS constants (tile 18480 / 73920, lane-split 147504, register-tile staging 9216 / 36864 bytes)");
+	BsDevKnobs knobs[4];  // the product build's, then BN_SPLIT=0, BN_SPLIT=1, BN_RR_LAST=0
+	knobs[1].split = 0;
+	knobs[2].split = 1;
+	knobs[3].rr_last = 0;
+	std::vector<int> hits(kNttInstanceCount, 0);
+	int plans = 0;
+	static bool holds[4][3][33][5];  // (role, fmax 8 / 16 / 32) occurs in the plan of (log_h, log_rate)
+	bool planned = true, listed = true, geom = true, family = true;
+	for (int log_h = 12; log_h <= 32; log_h++)
+		for (int r = 0; r <= 4 && log_h + r <= 32; r++) {
+			plans++;
+			std::vector<uint32_t> s;
+			std::vector<BsPass> passes;
+			std::vector<RtPass> rt;
+			subspace_evals(log_h, r, s);
+			planned = planned && bs_supports(log_h, r) && plan_pass_tables(log_h, r, s, passes, rt) == BN_OK;
+			for (const BsPass& p : passes) {
+				const int fmax = pass_fmax(p), fi = fmax == 8 ? 0 : fmax == 16 ? 1 : 2;
+				planned = planned && (fmax == 8 || fmax == 16 || fmax == 32) && p.role >= 0 && p.role < 4;
+				holds[p.role][fi][log_h][r] = true;
+				for (int limbs : {1, 4})
+					for (int variant : {1, 4, 5})
+						for (int inv = 0; inv <= 1; inv++) {
+							// one transform (the inverse reads one coset block), then batches at two tiles per CU and above
+							const size_t one = ((size_t)1 << (inv ? 0 : r)) << p.n_outer;
+							const size_t large = std::max(one, (size_t)2 * kCus);
+							for (size_t ntiles : {one, large, 2 * large})
+								for (int kn = 0; kn < 4; kn++) {
+									const NttLaunch l = ntt_plan_launch(limbs, variant, inv != 0, p.role, fmax, ntiles, kCus, knobs[kn]);
+									if (l.instance < 0 || l.instance >= kNttInstanceCount) {
+										listed = false;
+										continue;
+									}
+									const NttInstance& k = kNttInstances[l.instance];
+									if (kn == 0) hits[l.instance]++;
+									const bool split = k.family == NttFamily::Bs3, reg = k.family == NttFamily::Rr;
+									geom = geom && l.grid == ntiles && l.threads == (split ? 512u : 64u * (unsigned)limbs) && l.lds <= 160 * 1024 &&
+									       l.lds == (split ? kSplitLdsBytes : reg ? rr::lds_bytes(limbs) : tile_lds_bytes(limbs));
+									family = family && k.limbs == limbs && (k.family == NttFamily::InvBs) == (inv != 0) &&
+									         (variant != 1 || (!reg && (limbs == 4 || !split))) && (variant != 4 || inv || reg);
+								}
+						}
+			}
+		}
+	check(planned && plans == 95, "NTT planner: pass tables of log_rate 0..4 x log_h 12..32-log_rate, 95 plans");
+	check(listed, "NTT planner: every selection is an entry of the instance list (product knobs, BN_SPLIT 0 / 1, BN_RR_LAST 0)");
+	bool live = true;
+	for (int i = 0; i < kNttInstanceCount; i++) live = live && hits[i] > 0;
+	check(live, "NTT planner: every entry of the instance list is selected under the product knobs");
+	check(geom, "NTT planner: workgroup size and LDS bytes are the family's constants, LDS within 160 KiB");
+	check(family, "NTT planner: the instance's limbs, direction and variant are the launch's");
+	// which (role, fmax) pairs a plan can hold, and a smallest plan of each: at(..) = the pair occurs at
+	// (log_h, log_rate) and in no plan of a smaller log_h + log_rate (several plans can tie there)
+	auto never = [&](int role, int fi) {
+		for (int log_h = 12; log_h <= 32; log_h++)
+			for (int r = 0; r <= 4; r++)
+				if (holds[role][fi][log_h][r]) return false;
+		return true;
+	};
+	auto at = [&](int role, int fi, int log_h, int r) {
+		for (int h = 12; h <= 32; h++)
+			for (int q = 0; q <= 4; q++)
+				if (holds[role][fi][h][q] && h + q < log_h + r) return false;
+		return holds[role][fi][log_h][r];
+	};
+	check(at(ROLE_FIRST, 0, 13, 0) && at(ROLE_FIRST, 1, 17, 0) && at(ROLE_FIRST, 2, 17, 4), "NTT planner: FIRST at fmax 8 / 16 / 32 from (13,0) / (17,0) / (17,4)");
+	check(never(ROLE_MID, 0) && at(ROLE_MID, 1, 20, 0) && at(ROLE_MID, 2, 21, 0), "NTT planner: MID never at fmax 8, 16 / 32 from (20,0) / (21,0)");
+	check(never(ROLE_LAST, 0) && at(ROLE_LAST, 1, 13, 0) && at(ROLE_LAST, 2, 17, 0), "NTT planner: LAST never at fmax 8, 16 / 32 from (13,0) / (17,0)");
+	check(never(ROLE_SINGLE, 0) && at(ROLE_SINGLE, 1, 12, 0) && never(ROLE_SINGLE, 2), "NTT planner: SINGLE at fmax 16 only, (12,0)");
+
+	// hand-derived selections, one GF(2^128) transform at rate 0 under the default variant
+	auto plan_one = [&](int log_h, int variant, std::vector<BsPass>& passes) {
+		std::vector<uint32_t> s;
+		std::vector<RtPass> rt;
+		subspace_evals(log_h, 0, s);
+		std::vector<NttLaunch> ls;
+		if (plan_pass_tables(log_h, 0, s, passes, rt) != BN_OK) return ls;
+		for (const BsPass& p : passes) ls.push_back(ntt_plan_launch(4, variant, false, p.role, pass_fmax(p), (size_t)1 << p.n_outer, kCus, knobs[0]));
+		return ls;
+	};
+	std::vector<BsPass> passes;
+	std::vector<NttLaunch> ls = plan_one(24, 5, passes);
+	check(ls.size() == 3 && is(ls[0], NttFamily::Rr, 4, ROLE_FIRST, 8, 1) && is(ls[1], NttFamily::Bs, 4, ROLE_MID, 32, 0) &&
+	          is(ls[2], NttFamily::Bs, 4, ROLE_LAST, 32, 0) && ls[0].grid == 4096 && ls[2].grid == 4096,
+	      "NTT planner: 2^24 = antt_rr_pass<4,0,8>, antt_bs_pass<4,1,32>, antt_bs_pass<4,2,32>, 4096 tiles each");
+	ls = plan_one(20, 5, passes);
+	check(ls.size() == 3 && is(ls[0], NttFamily::Rr, 4, ROLE_FIRST, 8, 1) && is(ls[1], NttFamily::Bs3, 4, ROLE_MID, 0, 0) && ls[1].threads == 512 &&
+	          is(ls[2], NttFamily::Rr, 4, ROLE_LAST, 32, 1) && ls[2].grid == 256,
+	      "NTT planner: one 2^20 transform = antt_rr_pass<4,0,8>, lane-split antt_bs3_pass<1>, antt_rr_pass<4,2,32,1>");
+	ls = plan_one(12, 5, passes);
+	check(ls.size() == 1 && pass_fmax(passes[0]) == 16 && is(ls[0], NttFamily::Bs, 4, ROLE_SINGLE, 32, 0), "NTT planner: 2^12 = SINGLE at fmax 16, antt_bs_pass<4,3,32>");
+	ls = plan_one(12, 4, passes);
+	check(ls.size() == 1 && is(ls[0], NttFamily::Rr, 4, ROLE_SINGLE, 16, 3), "NTT planner: 2^12 under variant 4 = antt_rr_pass<4,3,16>");
+	// a batch that leaves the small launches takes the bounded bottom instance and the LDS-tile upper pass
+	const NttLaunch big = ntt_plan_launch(4, 4, false, ROLE_LAST, 32, 512, kCus, knobs[0]);
+	check(is(big, NttFamily::Rr, 4, ROLE_LAST, 32, 3) && is(ntt_plan_launch(4, 5, false, ROLE_LAST, 32, 512, kCus, knobs[0]), NttFamily::Bs, 4, ROLE_LAST, 32, 0) &&
+	          is(ntt_plan_launch(4, 5, false, ROLE_FIRST, 32, 512, kCus, knobs[0]), NttFamily::Bs, 4, ROLE_FIRST, 32, 0),
+	      "NTT planner: at two tiles per CU the bottom pass is bounded to three waves and the upper pass leaves the lane-split kernel");
+	// the inverse runs the forward's passes in reverse: forward pass 0 is its compact-out top pass
+	check(is(ntt_plan_launch(4, 5, true, ROLE_FIRST, 8, 4096, kCus, knobs[0]), NttFamily::InvBs, 4, ROLE_LAST, 8, 0) &&
+	          is(ntt_plan_launch(1, 1, true, ROLE_LAST, 16, 16, kCus, knobs[0]), NttFamily::InvBs, 1, ROLE_FIRST, 32, 0),
+	      "NTT planner: inverse roles are the forward's mirrored, fmax 16 on the GF(2^32) form");
+	// development-build switches choose only among listed instances, and only where they apply
+	check(is(ntt_plan_launch(4, 5, false, ROLE_MID, 32, 4096, kCus, knobs[2]), NttFamily::Bs3, 4, ROLE_MID, 0, 0) &&
+	          is(ntt_plan_launch(1, 5, false, ROLE_MID, 32, 16, kCus, knobs[2]), NttFamily::Bs, 1, ROLE_MID, 32, 0) &&
+	          is(ntt_plan_launch(4, 5, false, ROLE_FIRST, 32, 16, kCus, knobs[1]), NttFamily::Bs, 4, ROLE_FIRST, 32, 0) &&
+	          is(ntt_plan_launch(4, 5, false, ROLE_LAST, 32, 256, kCus, knobs[3]), NttFamily::Bs, 4, ROLE_LAST, 32, 0),
+	      "NTT planner: BN_SPLIT and BN_RR_LAST move a launch between listed instances");
+	check(ntt_plan_launch(4, 0, false, ROLE_FIRST, 8, 16, kCus, knobs[0]).instance == -1 && ntt_plan_launch(4, 2, false, ROLE_FIRST, 8, 16, kCus, knobs[0]).instance == -1,
+	      "NTT planner: variants without bitsliced passes select nothing");
+	check(valid_variant(0) && valid_variant(1) && valid_variant(4) && valid_variant(5) && !valid_variant(2) && !valid_variant(3) && !valid_variant(6) && !valid_variant(-1),
+	      "NTT planner: variants 0, 1, 4, 5");
+}
+
 static void library_host_checks() {
 	std::mt19937_64 rng(11);
 	check(bn_version() && std::strlen(bn_version()) > 0, "bn_version");
@@ -362,15 +494,15 @@ static void library_host_checks() {
 	}
 	check(ok, "library bn_sumcheck_interpolate vs oracle");
 
-	// the host-only pass planner (csrc/antt_passes.cpp) over every size it plans: log_h 12..28 x
-	// log_rate 0..4, each output in a heap allocation of exactly the size the call asks for
+	// the host-only pass planner (csrc/antt_passes.cpp) over every size it plans: log_rate 0..4 x
+	// log_h 12..32 - log_rate, each output in a heap allocation of exactly the size the call asks for
 	{
 		uint32_t probe[512];
 		check(bn_antt_inword_tables(12, 0, probe, 512) == BN_OK && probe[0] <= 512, "bn_antt_inword_tables reports its size");
 		const size_t words = probe[0];
 		bool tabs = true, classes = true;
-		for (int log_h = 12; log_h <= 28; log_h++)
-			for (int r = 0; r <= 4; r++) {
+		for (int log_h = 12; log_h <= 32; log_h++)
+			for (int r = 0; r <= 4 && log_h + r <= 32; r++) {
 				std::vector<uint32_t> t(words);
 				tabs = tabs && bn_antt_inword_tables(log_h, r, t.data(), t.size()) == BN_OK && t[0] == words &&
 				       (int)t[4] == log_h - 12;  // the bottom pass fixes every index bit above its tile
@@ -384,8 +516,8 @@ static void library_host_checks() {
 				for (size_t i = 0; i < n; i++)
 					classes = classes && (c[i] == 0 || c[i] == 2 || c[i] == 4 || c[i] == 8 || c[i] == 16 || c[i] == 32);
 			}
-		check(tabs, "bn_antt_inword_tables, log_h 12..28 x log_rate 0..4");
-		check(classes, "bn_antt_stage_classes, log_h 12..28 x log_rate 0..4");
+		check(tabs, "bn_antt_inword_tables, log_rate 0..4 x log_h 12..32 - log_rate");
+		check(classes, "bn_antt_stage_classes, log_rate 0..4 x log_h 12..32 - log_rate");
 		std::vector<uint32_t> t(words);
 		std::vector<int32_t> c(4);
 		check(bn_antt_inword_tables(11, 0, t.data(), t.size()) == BN_ERR_UNSUPPORTED, "bn_antt_inword_tables rejects log_h 11");
@@ -484,6 +616,7 @@ int main() {
 	library_host_checks();
 	buffer_check_checks();
 	sumcheck_planner_checks();
+	ntt_planner_checks();
 	failures += conformance::run_all(2);
 	std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "PASSED", failures);
 	return failures ? 1 : 0;

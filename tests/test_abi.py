@@ -71,3 +71,19 @@ def test_product_library_has_no_experiment_kernels():
     # planner): sc_fold<2, *>, sc_fold<0, 4>, sc_messages<1, 4>, sc_messages<2, 16>
     for name in (b"sc_foldILi2E", b"sc_foldILi0ELi4E", b"sc_messagesILi1ELi4E", b"sc_messagesILi2ELi16E"):
         assert name not in blob, name
+    # additive-NTT pass instantiations that no plan selects (the same program sweeps ntt_plan_launch
+    # over every plan): only a first pass (roles: 0 first, 1 mid, 2 last, 3 single; the inverse's
+    # last) has every twiddle in GF(2^8), and a single pass (log_h 12) lies in GF(2^16).
+    # Template arguments <limbs, role, fmax[, waves bound]>; a kept instance of each family first
+    for name in (b"antt_bs_passILi4ELi2ELi32E", b"antt_bs_passILi1ELi0ELi8E", b"antt_bs3_passILi1E", b"antt_inv_bs_passILi4ELi2ELi8E",
+                 b"antt_inv_bs_passILi1ELi0ELi32E", b"antt_rr_passILi4ELi0ELi8ELi1E", b"antt_rr_passILi1ELi3ELi16ELi3E",
+                 b"antt_rr_passILi4ELi2ELi32ELi1E"):
+        assert name in blob, name
+    gone = [b"antt_bs_passILi%dELi%dELi8E" % (l, role) for l in (1, 4) for role in (1, 2, 3)]
+    gone += [b"antt_inv_bs_passILi%dELi%dELi8E" % (l, role) for l in (1, 4) for role in (0, 1, 3)]
+    gone += [b"antt_rr_passILi%dELi%sE" % (l, args) for l in (1, 4)
+             for args in (b"1ELi8ELi1", b"2ELi8ELi3", b"3ELi8ELi3", b"3ELi32ELi3")]
+    gone += [b"antt_rr_passILi4ELi2ELi8ELi1E"]
+    assert len(gone) == 21
+    for name in gone:
+        assert name not in blob, name

@@ -4,7 +4,7 @@ GF(2^8) circuits, 16 early and 16 after the circuit in the other GF(2^32) kernel
 in-word stages of the bottom pass and the scalar top stage run the same body (bs_pass_body,
 csrc/antt_bs.hip). Parity with the oracle at the smallest
 launches that are not small launches: at least two tiles per CU, below which the default plan
-takes the lane-split and register-tile kernels instead (small_launch, csrc/antt_bs.hpp).
+takes the lane-split and register-tile kernels instead (ntt_plan_launch, csrc/antt_passes.cpp).
 
 * 2^13 at log_rate 1, 128 transforms: 2 tiles x 2 cosets x 128 = 512 bottom tiles. A one-stage upper
   pass over the packed bottom kernel (GF(2^16) twiddles on the FMAX 32 kernel; the LDS-tile plan
