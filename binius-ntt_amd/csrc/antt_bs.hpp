@@ -20,17 +20,11 @@ inline NttLaunch plan_pass(const bn_antt_plan* plan, const BsPass& pass, bool in
 }
 
 // Entry `instance` of kNttInstances as a kernel (antt.hip asks the file of its family); each file
-// instantiates its families' entries of the list through instance_table
+// instantiates its families' entries of the list through instance_table (common.hpp)
 const void* ntt_kernel_fn(int instance);
 const void* bs_kernel_fn(int instance);   // antt_bs.hip: antt_bs_pass, antt_bs3_pass
 const void* rr_kernel_fn(int instance);   // antt_rr.hip: antt_rr_pass
 const void* inv_kernel_fn(int instance);  // antt_inv.hip: antt_inv_bs_pass
-// fns[i] = At<i>::fn() over the whole list (nullptr where At leaves an entry to another file)
-template <template <int> class At, size_t... I>
-const void* instance_table(int instance, std::index_sequence<I...>) {
-	static const void* const fns[] = {At<(int)I>::fn()...};
-	return fns[instance];
-}
 
 // Bitsliced fast path, used when bs_supports(log_h, log_rate)
 int launch_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, size_t batch, hipStream_t st);

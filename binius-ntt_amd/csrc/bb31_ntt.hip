@@ -17,22 +17,18 @@
 // products are Montgomery multiplications by Montgomery-encoded twiddles (risc0_baby_bear.h
 // mul, lines 172-180, so w * R is stored). A bit-reversed input (DataOrder::BIT_REVERSED) is
 // read through the first pass's addressing: the reads stay runs of 2^{m_1} words.
+// The digit split, the pass tables, the twiddle table and the launch of every pass are planned on
+// the host (bb31_plan.cpp); this file holds the kernels and launches what the planner says.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdlib>
-#include <vector>
-
+#include "bb31_plan.hpp"
 #include "common.hpp"
 
 struct bn_bb31_ntt_plan {
 	int device = 0;
-	int log_n = 0, log_group = 0;
-	uint32_t generator = 0;  // canonical
-	int L = 0;
-	int m[4] = {0, 0, 0, 0};
-	uint32_t* wtab = nullptr;  // Montgomery-encoded w^e: lo table [4096] then hi table [2^(log_n-12)] (or one table)
-	uint32_t* scratch = nullptr;
+	bn::bb31::BbPlan plan{};   // the passes, built once
+	uint32_t* wtab = nullptr;  // bb_twiddles: Montgomery-encoded w^e
+	uint32_t* scratch = nullptr;  // passes 1..L-1 run in place here: n * batch words, grown on demand
 	size_t scratch_words = 0;
 	hipStream_t own_stream = nullptr;
 	uint32_t* h_dev = nullptr;  // host-apply staging (in, out)
@@ -40,14 +36,9 @@ struct bn_bb31_ntt_plan {
 
 namespace bn {
 namespace {
+using namespace bb31;
 
-constexpr uint32_t kP = 2013265921u;    // 15 * 2^27 + 1
 constexpr uint32_t kPinv = 0x88000001u;  // p^-1 mod 2^32 (risc0::Fp::M)
-constexpr uint32_t kR2 = 1172168163u;    // 2^64 mod p (risc0::Fp::R2)
-constexpr int kCols = 32;
-constexpr int kMaxM = 9;
-constexpr int kThreads = 256;
-constexpr int kLoBits = 12;
 
 __host__ __device__ inline uint32_t mont(uint32_t a, uint32_t b) {
 	uint64_t o = (uint64_t)a * b;
@@ -65,28 +56,6 @@ __host__ __device__ inline uint32_t bb_reduce(uint32_t x) {  // any u32 -> canon
 	x = x >= kP ? x - kP : x;
 	return x >= kP ? x - kP : x;
 }
-static uint32_t h_mul(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) % kP); }
-static uint32_t h_pow(uint32_t x, uint64_t e) {
-	uint32_t r = 1;
-	while (e) {
-		if (e & 1) r = h_mul(r, x);
-		x = h_mul(x, x);
-		e >>= 1;
-	}
-	return r;
-}
-
-struct BbPass {
-	int m;          // digit bits of this pass
-	int role;       // 0 first/middle (rows stride Mp, 32-column tiles), 1 last, 2 single (whole array)
-	int log_mp;     // log2 M_p (columns of the sub-problem; 0 for the last pass)
-	int log_sub;    // log2 M_{p-1} (size of the sub-problem)
-	int bitrev_in;  // first pass reading a bit-reversed input
-	// last pass: k_1 has m_1 bits; (k_2..k_{L-1}) has gbits bits
-	int m1, gbits;
-	int log_pos[4], log_out[4], mdig[4];  // digits 2..L-1: position stride, output stride, bits
-	int ndig;
-};
 
 struct BbArgs {
 	const uint32_t* src;
@@ -106,8 +75,9 @@ __device__ inline uint32_t wpow(const BbArgs& A, uint32_t e) {
 
 __device__ inline uint32_t rev_bits(uint32_t v, int bits) { return bits ? __brev(v) >> (32 - bits) : 0u; }
 
-// tile element (row r, column c) <-> words, per role
-template <int ROLE>
+// The single-tile kernel (role 2, log_n <= kMaxSingleM): the whole transform is one column of
+// R = 2^m rows in LDS, row r at lds[r]; behind it the tile DFT's twiddles w_R^i (Montgomery-encoded),
+// i < R/2 (bb_lds_bytes).
 __global__ __launch_bounds__(kThreads) void bb_pass(BbArgs A) {
 	extern __shared__ uint32_t lds[];
 	const BbPass& ps = A.p;
@@ -117,58 +87,20 @@ __global__ __launch_bounds__(kThreads) void bb_pass(BbArgs A) {
 	const size_t b = blockIdx.y;  // transform of the batch
 	const uint32_t* src = A.src + b * A.n;
 	uint32_t* dst = A.dst + b * A.n;
-	const size_t t = blockIdx.x;
-	// tile geometry
-	size_t q = 0, cb = 0, g = 0, kb = 0;
-	if (ROLE == 0) {
-		const size_t ncb = ((size_t)1 << ps.log_mp) / kCols;
-		q = t / ncb;
-		cb = t % ncb;
-	} else if (ROLE == 1) {
-		const size_t nkb = ((size_t)1 << ps.m1) / kCols;
-		g = t / nkb;
-		kb = t % nkb;
-	}
-	size_t gpos = 0, gout = 0;
-	if (ROLE == 1) {
-		size_t gg = g;
-		for (int i = 0; i < ps.ndig; i++) {
-			const size_t d = gg & (((size_t)1 << ps.mdig[i]) - 1);
-			gg >>= ps.mdig[i];
-			gpos += d << ps.log_pos[i];
-			gout += d << ps.log_out[i];
-		}
-	}
-	const int cols = ROLE == 2 ? 1 : kCols;
-	const int W = ROLE == 2 ? R : R * kCols;  // words in the tile
-	auto src_addr = [&](int r, int c) -> size_t {
-		if (ROLE == 0) {
-			const size_t j = (q << ps.log_sub) + ((size_t)r << ps.log_mp) + cb * kCols + c;
-			return ps.bitrev_in ? (size_t)rev_bits((uint32_t)j, A.log_n) : j;
-		}
-		if (ROLE == 1) return ((kb * kCols + c) << (A.log_n - ps.m1)) + gpos + r;
-		return ps.bitrev_in ? (size_t)rev_bits((uint32_t)r, A.log_n) : (size_t)r;
-	};
-	// LDS: row r, column c at r * cols + c (a row of 32 words spans half the banks); behind the
-	// tile, the tile DFT's twiddles w_R^i (Montgomery-encoded), i < R/2
-	uint32_t* twl = lds + W;
+	uint32_t* twl = lds + R;
 	for (int i = tid; i < R / 2; i += kThreads) twl[i] = wpow(A, (uint32_t)i << (A.log_n - m));
-	for (int u = tid; u < W; u += kThreads) {
-		const int r = u / cols, c = u % cols;
-		lds[u] = bb_reduce(src[src_addr(r, c)]);
-	}
+	for (int r = tid; r < R; r += kThreads)
+		lds[r] = bb_reduce(src[ps.bitrev_in ? (size_t)rev_bits((uint32_t)r, A.log_n) : (size_t)r]);
 	__syncthreads();
 	// radix-2 DIF stages: natural-order rows in, bit-reversed rows out; stage st uses
 	// w_{2 half}^k = w_R^(k R / (2 half))
-	const int pairs = (R / 2) * cols;
 	for (int st = m - 1; st >= 0; st--) {
 		const int half = 1 << st;
-		for (int u = tid; u < pairs; u += kThreads) {
-			const int c = u % cols, pr = u / cols;
+		for (int pr = tid; pr < R / 2; pr += kThreads) {
 			const int k = pr & (half - 1);
 			const int r0 = ((pr >> st) << (st + 1)) | k;
-			uint32_t* pu = lds + r0 * cols + c;
-			uint32_t* pv = pu + half * cols;
+			uint32_t* pu = lds + r0;
+			uint32_t* pv = pu + half;
 			const uint32_t x = *pu, y = *pv;
 			*pu = bb_add(x, y);
 			const uint32_t d = bb_sub(x, y);
@@ -176,38 +108,15 @@ __global__ __launch_bounds__(kThreads) void bb_pass(BbArgs A) {
 		}
 		__syncthreads();
 	}
-	// write row k (held at LDS row rev_m(k)). ROLE 0: inter-pass twiddle w_{M_{p-1}}^(c k); a
-	// lane keeps its column c and walks rows k = k0, k0 + 8, ... so the twiddle advances by one
-	// Montgomery product per element from two table lookups per lane.
-	if (ROLE == 0) {
-		const int c = tid % kCols, k0 = tid / kCols;  // kThreads / kCols = 8 rows per sweep
-		const size_t cf = cb * kCols + c;             // column index inside the sub-problem
-		const size_t msk = ((size_t)1 << ps.log_sub) - 1;
-		const int sh = A.log_n - ps.log_sub;
-		uint32_t tw = wpow(A, (uint32_t)(((cf * (size_t)k0) & msk) << sh));
-		const uint32_t step = wpow(A, (uint32_t)(((cf * (size_t)(kThreads / kCols)) & msk) << sh));
-		for (int k = k0; k < R; k += kThreads / kCols) {
-			const uint32_t v = mont(lds[rev_bits((uint32_t)k, m) * kCols + c], tw);
-			dst[(q << ps.log_sub) + ((size_t)k << ps.log_mp) + cf] = v;
-			tw = mont(tw, step);
-		}
-	} else {
-		for (int u = tid; u < W; u += kThreads) {
-			const int k = u / cols, c = u % cols;
-			const uint32_t v = lds[rev_bits((uint32_t)k, m) * cols + c];
-			if (ROLE == 1)
-				dst[(kb * kCols + c) + gout + ((size_t)k << (A.log_n - m))] = v;
-			else
-				dst[k] = v;
-		}
-	}
+	for (int k = tid; k < R; k += kThreads) dst[k] = lds[rev_bits((uint32_t)k, m)];  // row k is held at LDS row rev_m(k)
 }
 
-// Register-resident variant for the multi-pass roles (0, 1) and M = m in [6, 9]: the same tile,
-// twiddles and output as bb_pass, but a thread holds E = R/8 elements of one column, rows
+// The multi-pass roles (0 first/middle, 1 last), M = m in [kMinM, kMaxM]: a tile of R = 2^M rows x
+// kCols columns, register-resident. A thread holds E = R/8 elements of one column, rows
 // t + 8i, so the radix-2 stages with half >= 8 run in registers; one LDS exchange regroups the
 // column into runs of 8 rows for the last three stages. LDS traffic per tile: the exchange and the
-// output gather, instead of two reads and two writes per element per stage.
+// output gather. LDS: row r, column c at r * kCols + c (a row of 32 words spans half the banks),
+// the tile DFT's twiddles behind the tile as in bb_pass.
 template <int ROLE, int M>
 __global__ __launch_bounds__(kThreads) void bb_pass_r(BbArgs A) {
 	constexpr int R = 1 << M, E = R / 8;
@@ -292,7 +201,9 @@ __global__ __launch_bounds__(kThreads) void bb_pass_r(BbArgs A) {
 #pragma unroll
 		for (int j = 0; j < 8; j++) lds[(8 * (t + 8 * u) + j) * kCols + c] = x[8 * u + j];
 	__syncthreads();
-	// output: as bb_pass (row k sits at LDS row rev_M(k))
+	// write row k (held at LDS row rev_M(k)). ROLE 0: inter-pass twiddle w_{M_{p-1}}^(c k); a
+	// lane keeps its column and walks rows k = k0, k0 + 8, ... so the twiddle advances by one
+	// Montgomery product per element from two table lookups per lane.
 	if (ROLE == 0) {
 		const int cc = tid % kCols, k0 = tid / kCols;
 		const size_t cf = cb * kCols + cc;
@@ -315,80 +226,63 @@ __global__ __launch_bounds__(kThreads) void bb_pass_r(BbArgs A) {
 	}
 }
 
-template <int ROLE>
-static const void* pass_fn() {
-	return (const void*)bb_pass<ROLE>;
-}
-
-static const void* pass_r_fn(int role, int m) {
-	static const void* r[2][4] = {
-	    {(const void*)bb_pass_r<0, 6>, (const void*)bb_pass_r<0, 7>, (const void*)bb_pass_r<0, 8>, (const void*)bb_pass_r<0, 9>},
-	    {(const void*)bb_pass_r<1, 6>, (const void*)bb_pass_r<1, 7>, (const void*)bb_pass_r<1, 8>, (const void*)bb_pass_r<1, 9>}};
-	return r[role][m - 6];
-}
-
-// the register variant where it applies (roles 0/1, m in 6..9); in the development build BN_BB_LDS=1
-// forces bb_pass (A/B)
-static const void* pass_fn_for(const BbPass& p) {
-#ifdef BN_DEV
-	static const bool lds_only = getenv("BN_BB_LDS") != nullptr;
-#else
-	constexpr bool lds_only = false;
-#endif
-	if (!lds_only && p.role != 2 && p.m >= 6 && p.m <= 9) return pass_r_fn(p.role, p.m);
-	return p.role == 0 ? pass_fn<0>() : p.role == 1 ? pass_fn<1>() : pass_fn<2>();
-}
-
-static std::vector<BbPass> bb_passes(const bn_bb31_ntt_plan* P, bool bitrev_in) {
-	std::vector<BbPass> v;
-	const int n = P->log_n;
-	if (P->L == 1) {
-		BbPass p{};
-		p.m = n;
-		p.role = 2;
-		p.bitrev_in = bitrev_in;
-		v.push_back(p);
-		return v;
+// entry I of kBbInstances as a kernel
+template <int I>
+struct BbAt {
+	static const void* fn() {
+		constexpr BbInstance k = kBbInstances[I];
+		if constexpr (k.role == BB_SINGLE) return (const void*)bb_pass;
+		else return (const void*)bb_pass_r<k.role, k.m>;
 	}
-	int used = 0;
-	for (int i = 0; i < P->L; i++) {
-		BbPass p{};
-		p.m = P->m[i];
-		p.log_sub = n - used;
-		used += p.m;
-		p.log_mp = n - used;
-		if (i + 1 < P->L) {
-			p.role = 0;
-			p.bitrev_in = i == 0 && bitrev_in;
-		} else {
-			p.role = 1;
-			p.m1 = P->m[0];
-			// digits 2..L-1: position stride M_i = 2^(n - m_1 - ... - m_i), output stride N_1 ... N_{i-1}
-			int pos_used = P->m[0], out_used = P->m[0];
-			p.ndig = 0;
-			for (int d = 1; d + 1 < P->L; d++) {
-				pos_used += P->m[d];
-				p.log_pos[p.ndig] = n - pos_used;
-				p.log_out[p.ndig] = out_used;
-				p.mdig[p.ndig] = P->m[d];
-				out_used += P->m[d];
-				p.ndig++;
-			}
-			p.gbits = n - P->m[0] - P->m[P->L - 1];
-		}
-		v.push_back(p);
-	}
-	return v;
-}
+};
+const void* bb_kernel_fn(int instance) { return instance_table<BbAt>(instance, std::make_index_sequence<kBbInstanceCount>()); }
 
-// the device side of a new plan: the twiddle table, and the LDS attribute of every pass kernel
-static int bb_plan_to_device(bn_bb31_ntt_plan* P, const std::vector<uint32_t>& tab) {
+// the device side of a new plan: the twiddle table, and the LDS attribute of every instance
+int bb_plan_to_device(bn_bb31_ntt_plan* P, const std::vector<uint32_t>& tab) {
 	BN_DEVICE_SCOPE(P->device);
 	if (int rc = dev_alloc(&P->wtab, tab.size() * sizeof(uint32_t))) return rc;
 	BN_HIP(hipMemcpy(P->wtab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	for (const void* f : {pass_fn<0>(), pass_fn<1>(), pass_fn<2>(), pass_r_fn(0, 6), pass_r_fn(0, 7), pass_r_fn(0, 8),
-	                      pass_r_fn(0, 9), pass_r_fn(1, 6), pass_r_fn(1, 7), pass_r_fn(1, 8), pass_r_fn(1, 9)})
-		BN_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, ((1 << kMaxM) * kCols + (1 << 12)) * 4));
+	for (int i = 0; i < kBbInstanceCount; i++)
+		BN_HIP(hipFuncSetAttribute(bb_kernel_fn(i), hipFuncAttributeMaxDynamicSharedMemorySize,
+		                           (int)bb_lds_bytes(kBbInstances[i].role, kBbInstances[i].m)));
+	return BN_OK;
+}
+
+// the scratch buffer at `words` words or more: grown on demand, freed with the plan
+int bb_scratch(bn_bb31_ntt_plan* P, size_t words) {
+	if (P->scratch_words >= words) return BN_OK;
+	if (P->scratch) BN_HIP(hipFree(P->scratch));
+	P->scratch = nullptr;
+	P->scratch_words = 0;
+	if (int rc = dev_alloc(&P->scratch, words * sizeof(uint32_t))) return rc;
+	P->scratch_words = words;
+	return BN_OK;
+}
+
+int bb_forward(bn_bb31_ntt_plan* P, const uint32_t* d_in, uint32_t* d_out, size_t batch, int bitrev, hipStream_t st) {
+	const BbPlan& pl = P->plan;
+	BbArgs A;
+	A.wtab = P->wtab;
+	A.n = (size_t)1 << P->plan.log_n;
+	A.log_n = P->plan.log_n;
+	A.hi_split = bb_hi_split(P->plan.log_n);
+	// passes 1..L-1 run in place on a scratch buffer (first pass: in -> scratch), the last pass
+	// scatters scratch -> out (its reads and writes are different index sets)
+	uint32_t* work = d_out;
+	if (pl.n_passes > 1) {
+		if (int rc = bb_scratch(P, A.n * batch)) return rc;
+		work = P->scratch;
+	}
+	for (int i = 0; i < pl.n_passes; i++) {
+		A.src = i == 0 ? d_in : work;
+		A.dst = i + 1 == pl.n_passes ? d_out : work;
+		A.p = pl.pass[i];
+		if (i == 0) A.p.bitrev_in = bitrev != 0;
+		const BbLaunch l = bb_plan_launch(A.p, P->plan.log_n, batch);
+		if (l.instance < 0) BN_FAIL(BN_ERR_UNSUPPORTED, "no kernel instance for role %d, m %d", A.p.role, A.p.m);
+		void* args[] = {&A};
+		BN_HIP(hipLaunchKernel(bb_kernel_fn(l.instance), dim3((unsigned)l.tiles, (unsigned)l.batch), dim3(l.threads), args, l.lds, st));
+	}
 	return BN_OK;
 }
 
@@ -401,48 +295,15 @@ extern "C" int bn_bb31_ntt_plan_create(int device, uint32_t generator, int log_g
                                        bn_bb31_ntt_plan** out) {
 	BN_CHECK_ARG(out != nullptr, "out is NULL");
 	// NTTConfRad2 asserts (src/ulvt/ntt/nttconf.cuh:31-38)
-	BN_CHECK_ARG(log_n >= 1 && log_n <= 27, "log_n must be in [1, 27] (got %d)", log_n);
-	BN_CHECK_ARG(log_group_order >= log_n && log_group_order <= 27, "log_group_order must be in [log_n, 27]");
+	BN_CHECK_ARG(log_n >= 1 && log_n <= kMaxLogN, "log_n must be in [1, 27] (got %d)", log_n);
+	BN_CHECK_ARG(log_group_order >= log_n && log_group_order <= kMaxLogN, "log_group_order must be in [log_n, 27]");
 	int ndev = 0;
 	BN_HIP(hipGetDeviceCount(&ndev));
 	BN_CHECK_ARG(device >= 0 && device < ndev, "device %d out of range", device);
 	auto* P = new bn_bb31_ntt_plan();
 	P->device = device;
-	P->log_n = log_n;
-	P->log_group = log_group_order;
-	P->generator = generator % kP;
-	if (log_n <= 13) {
-		P->L = 1;
-		P->m[0] = log_n;
-	} else {
-		P->L = (log_n + kMaxM - 1) / kMaxM;
-		for (int i = 0; i < P->L; i++) P->m[i] = log_n / P->L + (i < log_n % P->L ? 1 : 0);
-	}
-	// twiddle tables: w^e * R mod p (Montgomery-encoded), e < 2^log_n
-	const uint32_t w = h_pow(P->generator, (uint64_t)1 << (log_group_order - log_n));
-	const uint32_t R = (uint32_t)(((uint64_t)1 << 32) % kP);
-	std::vector<uint32_t> tab;
-	if (log_n <= kLoBits) {
-		uint32_t cur = R;
-		for (size_t e = 0; e < ((size_t)1 << log_n); e++) {
-			tab.push_back(cur);
-			cur = h_mul(cur, w);
-		}
-	} else {
-		uint32_t cur = R;
-		for (size_t e = 0; e < ((size_t)1 << kLoBits); e++) {
-			tab.push_back(cur);
-			cur = h_mul(cur, w);
-		}
-		const uint32_t wh = h_pow(w, (uint64_t)1 << kLoBits);
-		cur = R;
-		for (size_t e = 0; e < ((size_t)1 << (log_n - kLoBits)); e++) {
-			tab.push_back(cur);
-			cur = h_mul(cur, wh);
-		}
-	}
-	(void)kR2;
-	if (const int rc = bb_plan_to_device(P, tab)) {
+	bb_plan(log_n, &P->plan);
+	if (const int rc = bb_plan_to_device(P, bb_twiddles(generator, log_group_order, log_n))) {
 		bn_bb31_ntt_plan_destroy(P);
 		return rc;
 	}
@@ -461,58 +322,12 @@ extern "C" int bn_bb31_ntt_plan_destroy(bn_bb31_ntt_plan* P) {
 	return BN_OK;
 }
 
-static int bb_forward(bn_bb31_ntt_plan* P, const uint32_t* d_in, uint32_t* d_out, size_t batch, int bitrev, hipStream_t st) {
-	const size_t n = (size_t)1 << P->log_n;
-	const auto passes = bb_passes(P, bitrev != 0);
-	// passes 1..L-1 run in place on a scratch buffer (first pass: in -> scratch), the last pass
-	// scatters scratch -> out (its reads and writes are different index sets)
-	uint32_t* work = d_out;
-	if (P->L > 1) {
-		if (P->scratch_words < n * batch) {
-			if (P->scratch) BN_HIP(hipFree(P->scratch));
-			P->scratch = nullptr;
-			P->scratch_words = 0;
-			if (int rc = dev_alloc(&P->scratch, n * batch * sizeof(uint32_t))) return rc;
-			P->scratch_words = n * batch;
-		}
-		work = P->scratch;
-	}
-	for (size_t i = 0; i < passes.size(); i++) {
-		BbArgs A;
-		A.src = i == 0 ? d_in : work;
-		A.dst = i + 1 == passes.size() ? d_out : work;
-		A.wtab = P->wtab;
-		A.n = n;
-		A.log_n = P->log_n;
-		A.hi_split = P->log_n > kLoBits;
-		A.p = passes[i];
-		const BbPass& p = passes[i];
-		size_t tiles;
-		int W;
-		if (p.role == 2) {
-			tiles = 1;
-			W = 1 << p.m;
-		} else if (p.role == 0) {
-			tiles = ((size_t)1 << (P->log_n - p.log_sub)) * (((size_t)1 << p.log_mp) / kCols);
-			W = (1 << p.m) * kCols;
-		} else {
-			tiles = ((size_t)1 << p.gbits) * (((size_t)1 << p.m1) / kCols);
-			W = (1 << p.m) * kCols;
-		}
-		void* args[] = {&A};
-		const void* fn = pass_fn_for(p);
-		BN_HIP(hipLaunchKernel(fn, dim3((unsigned)tiles, (unsigned)batch), dim3(kThreads), args,
-		                       ((size_t)W + ((size_t)1 << p.m) / 2) * 4, st));
-	}
-	return BN_OK;
-}
-
 extern "C" int bn_bb31_ntt_forward_device(bn_bb31_ntt_plan* P, const uint32_t* d_in, uint32_t* d_out, size_t batch,
                                           int in_bit_reversed, void* stream) {
 	BN_CHECK_ARG(P != nullptr, "plan is NULL");
 	BN_CHECK_ARG(d_in != nullptr && d_out != nullptr, "device buffers must be non-NULL");
 	BN_CHECK_ARG(batch >= 1 && batch <= 65535, "batch must be in [1, 65535]");
-	const size_t bytes = ((size_t)4 << P->log_n) * batch;
+	const size_t bytes = ((size_t)4 << P->plan.log_n) * batch;
 	BN_CHECK_IO_DISJOINT(d_in, bytes, d_out, bytes);
 	BN_DEVICE_SCOPE(P->device);
 	return bb_forward(P, d_in, d_out, batch, in_bit_reversed, (hipStream_t)stream);
@@ -524,8 +339,8 @@ extern "C" int bn_bb31_ntt_forward_host(bn_bb31_ntt_plan* P, const uint32_t* in,
                                         int in_bit_reversed) {
 	BN_CHECK_ARG(P != nullptr, "plan is NULL");
 	BN_CHECK_ARG(in != nullptr && out != nullptr, "host buffers must be non-NULL");
-	const size_t n = (size_t)1 << P->log_n;
-	BN_CHECK_ARG(in_elems == n, "input has %zu elements, plan expects 2^%d", in_elems, P->log_n);
+	const size_t n = (size_t)1 << P->plan.log_n;
+	BN_CHECK_ARG(in_elems == n, "input has %zu elements, plan expects 2^%d", in_elems, P->plan.log_n);
 	BN_DEVICE_SCOPE(P->device);
 	if (!P->h_dev)
 		if (int rc = dev_alloc(&P->h_dev, 2 * n * sizeof(uint32_t))) return rc;

@@ -76,6 +76,14 @@ int dev_alloc(T** p, size_t bytes) {
 
 namespace bn {
 
+// A list of kernel instances as kernels: fns[i] = At<i>::fn() over the whole list (nullptr where At
+// leaves an entry to another file)
+template <template <int> class At, size_t... I>
+const void* instance_table(int instance, std::index_sequence<I...>) {
+	static const void* const fns[] = {At<(int)I>::fn()...};
+	return fns[instance];
+}
+
 // A device allocation that is freed on the way out unless release() hands it to a plan or prover.
 struct DevBuf {
 	void* p = nullptr;

@@ -9,7 +9,8 @@
 //   * the library's host-side code: the generated bitsliced circuits behind multiply_unrolled<H>,
 //     the packed-subfield helpers, bn_sumcheck_interpolate, the sumcheck round planner
 //     (csrc/sc_rounds.cpp) over every round shape, the additive NTT's launch planner
-//     (csrc/antt_passes.cpp) over every plan, variant and direction, the buffer checks
+//     (csrc/antt_passes.cpp) over every plan, variant and direction, the BabyBear NTT's planner
+//     (csrc/bb31_plan.cpp) over every log_n with its tables interpreted on the host, the buffer checks
 //     (csrc/buf_check.hpp), and the argument-checking / error paths of the C-ABI, the staged host
 //     calls among them (no device present here: they must fail cleanly with a status code and leak
 //     nothing);
@@ -38,6 +39,7 @@
 #include "utils/common.hpp"
 #include "../../oracle/oracle.h"
 #include "antt_passes.hpp"
+#include "bb31_plan.hpp"
 #include "buf_check.hpp"
 #include "circuit_conformance.hpp"
 #include "sc_rounds.hpp"
@@ -437,6 +439,154 @@ static void ntt_planner_checks() {
 	      "NTT planner: variants 0, 1, 4, 5");
 }
 
+// What the BabyBear kernels take a plan's pass tables and twiddle table to mean, as plain host code on
+// canonical values: role 0 is a naive DFT down each column of each sub-problem, times the inter-pass
+// twiddle w_{M_{p-1}}^(c k), in place; role 1 gathers its rows by log_pos and scatters their DFT by
+// log_out; role 2 is the DFT of the whole array. Driven by the tables alone.
+static std::vector<uint32_t> bb31_interpret(const bn::bb31::BbPlan& pl, const std::vector<uint32_t>& tab, const std::vector<uint32_t>& in,
+                                            bool bit_reversed) {
+	using namespace bn::bb31;
+	const int n = pl.log_n;
+	const uint32_t r_inv = orc_bb31_inv((uint32_t)(((uint64_t)1 << 32) % kP));
+	auto wpow = [&](size_t e) {  // w^e out of the Montgomery-encoded table(s)
+		if (!bb_hi_split(n)) return orc_bb31_mul(tab[e], r_inv);
+		const uint32_t lo = tab[e & (((size_t)1 << kLoBits) - 1)], hi = tab[((size_t)1 << kLoBits) + (e >> kLoBits)];
+		return orc_bb31_mul(orc_bb31_mul(lo, r_inv), orc_bb31_mul(hi, r_inv));
+	};
+	auto rev = [&](size_t v) {
+		size_t r = 0;
+		for (int i = 0; i < n; i++) r |= ((v >> i) & 1) << (n - 1 - i);
+		return r;
+	};
+	std::vector<uint32_t> work((size_t)1 << n), out((size_t)1 << n);
+	for (int pi = 0; pi < pl.n_passes; pi++) {
+		BbPass p = pl.pass[pi];
+		if (pi == 0) p.bitrev_in = bit_reversed;
+		const size_t R = (size_t)1 << p.m;
+		std::vector<uint32_t> wr(R), col(R), y(R);
+		for (size_t i = 0; i < R; i++) wr[i] = wpow(i << (n - p.m));
+		const uint32_t* src = pi == 0 ? in.data() : work.data();
+		auto load = [&](size_t r, size_t j) { col[r] = src[p.bitrev_in ? rev(j) : j] % kP; };
+		auto dft = [&]() {
+			const uint32_t *x = col.data(), *w = wr.data();
+			for (size_t k = 0; k < R; k++) {
+				uint64_t acc = 0;
+				for (size_t j = 0; j < R; j++) acc = (acc + (uint64_t)x[j] * w[(j * k) & (R - 1)]) % kP;
+				y[k] = (uint32_t)acc;
+			}
+		};
+		if (p.role == BB_SINGLE) {
+			for (size_t r = 0; r < R; r++) load(r, r);
+			dft();
+			out = y;
+		} else if (p.role == BB_UPPER) {
+			for (size_t q = 0; q < (size_t)1 << (n - p.log_sub); q++)
+				for (size_t c = 0; c < (size_t)1 << p.log_mp; c++) {
+					for (size_t r = 0; r < R; r++) load(r, (q << p.log_sub) + (r << p.log_mp) + c);
+					dft();
+					for (size_t k = 0; k < R; k++)
+						work[(q << p.log_sub) + (k << p.log_mp) + c] =
+						    orc_bb31_mul(y[k], wpow(((c * k) & (((size_t)1 << p.log_sub) - 1)) << (n - p.log_sub)));
+				}
+		} else {
+			for (size_t k1 = 0; k1 < (size_t)1 << p.m1; k1++)
+				for (size_t g = 0; g < (size_t)1 << p.gbits; g++) {
+					size_t gg = g, gpos = 0, gout = 0;
+					for (int i = 0; i < p.ndig; i++) {
+						const size_t d = gg & (((size_t)1 << p.mdig[i]) - 1);
+						gg >>= p.mdig[i];
+						gpos += d << p.log_pos[i];
+						gout += d << p.log_out[i];
+					}
+					for (size_t r = 0; r < R; r++) load(r, (k1 << (n - p.m1)) + gpos + r);
+					dft();
+					for (size_t k = 0; k < R; k++) out[k1 + gout + (k << (n - p.m))] = y[k];
+				}
+		}
+	}
+	return out;
+}
+
+// The BabyBear NTT's planner (csrc/bb31_plan.cpp, host only): the digit split, the pass tables and the
+// launch of every log_n, which instance each size reaches first, the twiddle table against the oracle's
+// powers, and the interpreter above against the oracle's transform.
+static void bb31_planner_checks() {
+	using namespace bn::bb31;
+	BbPlan pl;
+	check(kBbInstanceCount == 9 && !bb_plan(0, &pl) && !bb_plan(kMaxLogN + 1, &pl) && kMaxLogN == 27, "BabyBear planner: 9 instances, log_n 1..27");
+	check(bb_lds_bytes(BB_SINGLE, 13) == 49152 && bb_lds_bytes(BB_UPPER, 9) == 66560 && bb_lds_bytes(BB_LAST, 6) == 8320,
+	      "BabyBear planner: LDS bytes (single 2^13 49152, 2^9 x 32 tile 66560, 2^6 x 32 tile 8320)");
+	bool split = true, tables = true, listed = true, cover = true, lds = true;
+	int first[kBbInstanceCount];
+	for (int& f : first) f = 0;
+	for (int log_n = 1; log_n <= kMaxLogN; log_n++) {
+		split = split && bb_plan(log_n, &pl) && pl.log_n == log_n && pl.n_passes >= 1 && pl.n_passes <= kMaxPasses &&
+		        (pl.n_passes == 1) == (log_n <= 13);
+		if (!split) break;
+		const int L = pl.n_passes;
+		int used = 0;
+		for (int i = 0; i < L; i++) {
+			const BbPass& p = pl.pass[i];
+			split = split && p.m >= 1 && (L == 1 || (p.m >= 6 && p.m <= 9));
+			tables = tables && p.role == (L == 1 ? BB_SINGLE : i + 1 < L ? BB_UPPER : BB_LAST) && p.bitrev_in == 0 &&
+			         p.log_sub == log_n - used && p.log_mp == p.log_sub - p.m;
+			used += p.m;
+			if (p.role == BB_LAST) {
+				int dsum = 0;
+				for (int d = 0; d < p.ndig; d++) dsum += p.mdig[d];
+				tables = tables && p.m1 == pl.pass[0].m && p.ndig == L - 2 && p.gbits + p.m1 + p.m == log_n && dsum == p.gbits;
+			}
+			for (size_t batch : {(size_t)1, (size_t)3, (size_t)65535}) {
+				const BbLaunch l = bb_plan_launch(p, log_n, batch);
+				if (l.instance < 0 || l.instance >= kBbInstanceCount) {
+					listed = false;
+					continue;
+				}
+				const BbInstance& k = kBbInstances[l.instance];
+				listed = listed && k.role == p.role && (p.role == BB_SINGLE ? p.m <= k.m : p.m == k.m);
+				cover = cover && l.tiles * bb_tile_words(p.role, p.m) == (size_t)1 << log_n && l.batch == batch && l.threads == 256;
+				lds = lds && l.lds == bb_lds_bytes(p.role, p.m) && l.lds <= bb_lds_bytes(k.role, k.m) && l.lds <= 160 * 1024;
+				if (!first[l.instance]) first[l.instance] = log_n;
+			}
+		}
+		split = split && used == log_n;
+	}
+	check(split, "BabyBear planner: digits sum to log_n, one pass up to 2^13, every multi-pass digit in 6..9");
+	check(tables, "BabyBear planner: roles, sub-problem sizes, gbits + m1 + m_last = log_n, sum(mdig) = gbits");
+	check(listed, "BabyBear planner: every launch names the listed instance of the pass's (role, m)");
+	check(cover, "BabyBear planner: tiles x tile words = 2^log_n, grid y = batch, 256 threads");
+	check(lds, "BabyBear planner: LDS bytes within the instance's attribute and 160 KiB");
+	// the whole list is live; the smallest log_n of each entry (list order: single, role 0 m 6..9, role 1 m 6..9)
+	const int want_first[kBbInstanceCount] = {1, 19, 14, 15, 17, 19, 14, 16, 18};
+	check(std::memcmp(first, want_first, sizeof first) == 0,
+	      "BabyBear planner: every instance is selected; first at log_n 1 (single), 14 (7s), 15 / 16 (8s), 17 / 18 (9s), 19 (6s)");
+
+	const uint32_t mont_r = (uint32_t)(((uint64_t)1 << 32) % kP);
+	for (int log_n : {10, 14}) {
+		const std::vector<uint32_t> tab = bb_twiddles(137, 27, log_n);
+		const uint32_t w = orc_bb31_pow(137, (uint64_t)1 << (27 - log_n));
+		const size_t lo = (size_t)1 << (bb_hi_split(log_n) ? kLoBits : log_n), hi = bb_hi_split(log_n) ? (size_t)1 << (log_n - kLoBits) : 0;
+		bool ok = tab.size() == lo + hi;
+		for (size_t e = 0; ok && e < lo; e++) ok = tab[e] == orc_bb31_mul(orc_bb31_pow(w, e), mont_r);
+		for (size_t e = 0; ok && e < hi; e++) ok = tab[lo + e] == orc_bb31_mul(orc_bb31_pow(w, e << kLoBits), mont_r);
+		check(ok, log_n == 10 ? "BabyBear planner: twiddle table at 2^10 (one table) = w^e 2^32" : "BabyBear planner: twiddle table at 2^14 (lo ++ hi) = w^e 2^32");
+	}
+	struct Case {
+		int log_n;
+		bool bit_reversed;
+		const char* what;
+	};
+	for (const Case& c : {Case{10, true, "BabyBear planner: interpreted tables = oracle at 2^10, bit-reversed (single tile)"},
+	                      Case{14, false, "BabyBear planner: interpreted tables = oracle at 2^14, in order (two passes)"},
+	                      Case{14, true, "BabyBear planner: interpreted tables = oracle at 2^14, bit-reversed"},
+	                      Case{19, false, "BabyBear planner: interpreted tables = oracle at 2^19, in order (three passes)"}}) {
+		std::vector<uint32_t> in((size_t)1 << c.log_n), want(in.size());
+		orc_mt_fill(0xdeadbeefu + (uint32_t)c.log_n, in.data(), in.size());
+		orc_bb31_ntt(in.data(), want.data(), c.log_n, 137, 27, c.bit_reversed);
+		check(bb_plan(c.log_n, &pl) && bb31_interpret(pl, bb_twiddles(137, 27, c.log_n), in, c.bit_reversed) == want, c.what);
+	}
+}
+
 static void library_host_checks() {
 	std::mt19937_64 rng(11);
 	check(bn_version() && std::strlen(bn_version()) > 0, "bn_version");
@@ -617,6 +767,7 @@ int main() {
 	buffer_check_checks();
 	sumcheck_planner_checks();
 	ntt_planner_checks();
+	bb31_planner_checks();
 	failures += conformance::run_all(2);
 	std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "PASSED", failures);
 	return failures ? 1 : 0;

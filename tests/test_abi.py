@@ -87,3 +87,8 @@ def test_product_library_has_no_experiment_kernels():
     assert len(gone) == 21
     for name in gone:
         assert name not in blob, name
+    # BabyBear NTT: the multi-pass roles 0 and 1 run on bb_pass_r<role, m> alone (the same program
+    # sweeps bb_plan_launch over log_n 1..27), so the LDS-tile kernel bb_pass has no role 0 / 1 forms
+    assert b"bb_pass_rILi0ELi6E" in blob
+    for name in (b"bb_passILi0E", b"bb_passILi1E"):
+        assert name not in blob, name

@@ -88,6 +88,35 @@ def test_gpu_bit_reversed_batched_vs_oracle(log_n, dev):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("log_n", [13, 14, 15, 16, 17, 18, 19])
+def test_gpu_every_kernel_instance_device_path(log_n, dev):
+    # the smallest sizes that reach the largest single tile (13) and each multi-pass instance:
+    # bb_pass_r<0|1, 7> at 14, <0, 8> at 15, <1, 8> at 16, <0, 9> at 17, <1, 9> at 18, <0|1, 6> at 19
+    import binius_ntt_amd as B
+    batch = 2
+    xs = np.stack([O.mt_fill(0x0B1 + b + log_n, 1 << log_n) for b in range(batch)])
+    ntt = B.NTT(B.NTTConfRad2(B.BB31(137), 27, log_n))
+    got = _dev_run(B, ntt, xs.reshape(-1), dev, batch=batch).reshape(batch, -1)
+    for b in range(batch):
+        assert np.array_equal(got[b], O.bb31_ntt(xs[b], log_n))
+
+
+@pytest.mark.gpu
+def test_gpu_scratch_grows_and_stays(dev):
+    # one plan, batch 1, 3, 1: the scratch buffer of the upper passes is allocated, grown, and then
+    # larger than the call needs
+    import binius_ntt_amd as B
+    log_n = 14
+    xs = np.stack([O.mt_fill(0x5C7 + b, 1 << log_n) for b in range(3)])
+    want = [O.bb31_ntt(x, log_n) for x in xs]
+    ntt = B.NTT(B.NTTConfRad2(B.BB31(137), 27, log_n))
+    for batch in (1, 3, 1):
+        got = _dev_run(B, ntt, xs[:batch].reshape(-1), dev, batch=batch).reshape(batch, -1)
+        for b in range(batch):
+            assert np.array_equal(got[b], want[b]), (batch, b)
+
+
+@pytest.mark.gpu
 def test_gpu_round_trip_2_24(dev):
     # the reference's "NTTBB31 round trip" (test_ntt.cu:154-187)
     import binius_ntt_amd as B
