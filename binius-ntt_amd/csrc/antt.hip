@@ -203,6 +203,12 @@ static int bs_prepare(bn_antt_plan* plan) {
 	// and never reaches a launch
 	int rc = plan_pass_tables(plan->log_h, plan->log_rate, plan->s_host, plan->passes, plan->rt);
 	if (rc != BN_OK) return rc;
+	std::vector<uint32_t> ut;
+	rc = plan_tile_starts(plan->log_rate, plan->passes, plan->starts, ut);
+	if (rc != BN_OK) return rc;
+	if (!plan->ut_dev)
+		if ((rc = dev_alloc(&plan->ut_dev, ut.size() * sizeof(uint32_t))) != BN_OK) return rc;
+	BN_HIP(hipMemcpy(plan->ut_dev, ut.data(), ut.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
 	int cus = 0;
 	BN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, plan->device));
 	plan->num_cus = std::max(cus, 1);
@@ -258,6 +264,7 @@ extern "C" int bn_antt_plan_destroy(bn_antt_plan* p) {
 	if (!p) return BN_OK;
 	DeviceScope ds(p->device);
 	if (p->s_dev) (void)hipFree(p->s_dev);
+	if (p->ut_dev) (void)hipFree(p->ut_dev);
 	if (p->h_dev_in) (void)hipFree(p->h_dev_in);
 	if (p->h_dev_out) (void)hipFree(p->h_dev_out);
 	for (const auto& q : p->pending) {

@@ -52,6 +52,8 @@ struct BsParams {
 	int log_h, log_rate;
 	unsigned long long* trace;  // BN_TRACE=1: per-wave phase timestamps (dev tool)
 	int dbg;  // timing experiments only (BN_DEBUG_FLAGS): 1 no loads, 2 no stores, 4 no multiplies
+	TileStart ts;        // the pass's tile start and the plan's chunk tables (plan_tile_starts)
+	const uint32_t* ut;
 	BsPass p;
 };
 
@@ -88,14 +90,18 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 	uint32_t* cu_w = lds + L * kPlane + l * kMaxStages;  // this wave's copy of the uniform twiddle parts
 	const size_t n = (size_t)1 << P.log_h;
 	const bool TR = BS_TRACE(P);
-	unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // load, block, in-word, store, (wave-)tiles, pre, mul, post
+	// load, block, in-word, store, (wave-)tiles, pre, mul, post; then the load phase's first two parts:
+	// start to last tile load issued, then to tile data complete (the rest of `load`: cu_w ready and
+	// the tile in LDS)
+	unsigned long long tr[kTraceSlots] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	auto ts = [&]() -> unsigned long long {
 		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 		return __builtin_amdgcn_s_memtime();
 	};
+	const unsigned long long t0 = TR ? ts() : 0;
 
 	// tile -> (outer bits, coset, batch) -> addresses
-	const TileAddr ta = tile_addr(ps, P.log_rate);
+	const TileAddr ta = tile_addr<LAST>(P.ts, P.log_rate);
 	const size_t outer_off = ta.outer_off;
 	uint32_t* const dst = P.dst + (((ta.batch << P.log_rate) + (size_t)ta.coset) * n) * L;
 	const uint32_t* const src = IN_COMPACT ? (P.src + ta.batch * n * L) : dst;
@@ -240,11 +246,21 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 		}
 	};
 
-	unsigned long long t0 = TR ? ts() : 0;
 	issue();
+	if (TR) {
+		const unsigned long long ti = ts();
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		tr[8] += ti - t0;
+		tr[9] += ts() - ti;
+	}
 
-	// workgroup-uniform twiddle part of every stage (outer + coset bits), one lane per stage
-	if (lane < ps.k) cu_w[lane] = uniform_tw(ps, lane, ta.outer, ta.coset, P.log_rate);
+	// workgroup-uniform twiddle part of every stage (outer + coset bits): four scalar row loads behind
+	// the tile's loads in program order, held in SGPRs while the tile moves into LDS and handed to
+	// cu_w after it (with the lane word live across the tile's loads and LDS writes instead,
+	// antt_bs_pass<4, FIRST, 8> takes 97 VGPRs against 96 and drops from five waves to four)
+	__builtin_amdgcn_sched_barrier(0);
+	uint32_t cu[kMaxStages];
+	uniform_tw_rows(P.ts, P.ut, ta.outer, ta.coset, cu);
 
 	// ---- tile into LDS
 	if (IN_COMPACT) {
@@ -264,6 +280,10 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 		for (int q = lane; q < kTileBlocks; q += 64) transpose_block(plane + q * kLimbStride);
 	} else {
 		plane_from_regs(plane, lane, gbuf);
+	}
+	{
+		const uint32_t cuv = uniform_tw_to_lanes(cu);  // stage j's word in lane j
+		if (lane < kMaxStages) cu_w[lane] = cuv;
 	}
 	wave_lds_sync();
 	unsigned long long t1 = 0;
@@ -398,8 +418,8 @@ __device__ __forceinline__ void bs_pass_body(const BsParams& P) {
 		tr[4] += 1;
 	}
 	if (TR && lane == 0) {
-		unsigned long long* o = P.trace + ((size_t)blockIdx.x * (NT / 64) + (tid >> 6)) * 8;
-		for (int i = 0; i < 8; i++) o[i] = tr[i];
+		unsigned long long* o = P.trace + ((size_t)blockIdx.x * (NT / 64) + (tid >> 6)) * kTraceSlots;
+		for (int i = 0; i < kTraceSlots; i++) o[i] = tr[i];
 	}
 }
 
@@ -432,10 +452,11 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 	const BsPass& ps = P.p;
 	const int tid = threadIdx.x;
 	const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-	// BN_TRACE (development build): per-wave cycles of load, block stages, store (tr[0], tr[1],
-	// tr[3]: antt_bs_pass's slots) and of the multiplies inside the block stages (tr[6])
+	// BN_TRACE (development build): per-wave cycles of load and its first two parts, block stages,
+	// store (tr[0], tr[8], tr[9], tr[1], tr[3]: antt_bs_pass's slots) and of the multiplies inside the
+	// block stages (tr[6])
 	const bool TR = BS_TRACE(P);
-	unsigned long long tr[8] = {0, 0, 0, 0, 1, 0, 0, 0}, tlast = TR ? __builtin_amdgcn_s_memtime() : 0;
+	unsigned long long tr[kTraceSlots] = {0, 0, 0, 0, 1, 0, 0, 0, 0, 0}, tlast = TR ? __builtin_amdgcn_s_memtime() : 0;
 	auto mark = [&](int k) {
 		if (!TR) return;
 		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -446,12 +467,11 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 	const int l = w & 3, half = w >> 2;  // limb plane, product half
 	uint32_t* const cu_w = lds + 8 * kPlane;  // workgroup-uniform twiddle part per stage
 	const size_t n = (size_t)1 << P.log_h;
-	const TileAddr ta = tile_addr(ps, P.log_rate);
+	const TileAddr ta = tile_addr(P.ts, P.log_rate);
 	const size_t ooff = ta.outer_off;
 	uint32_t* dst = P.dst + (((ta.batch << P.log_rate) + (size_t)ta.coset) * n) * L;
 	const uint32_t* src = IN_COMPACT ? (P.src + ta.batch * n * L) : dst;
 
-	if (tid < ps.k) cu_w[tid] = uniform_tw(ps, tid, ta.outer, ta.coset, P.log_rate);
 	// ---- tile into LDS copy 0: 4096 pieces of 16 bytes, 8 per thread, all loads in flight at once
 	constexpr int kRounds = (kTileBlocks * 8 * L + kSplitNT - 1) / kSplitNT;
 	uint4 g[kRounds];
@@ -465,6 +485,14 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 			g[r] = ld_stream(src + bitsliced_off<L>(ps, ooff, q, pl, j));
 		}
 	}
+	// workgroup-uniform twiddle part of every stage: scalar loads behind the tile's loads (every wave
+	// computes it, wave 0 writes it)
+	__builtin_amdgcn_sched_barrier(0);
+	const uint32_t cuv = uniform_tw_lanes(P.ts, P.ut, ta.outer, ta.coset);
+	if (tid < kMaxStages) cu_w[tid] = cuv;
+	mark(8);
+	if (TR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	mark(9);
 #pragma unroll
 	for (int r = 0; r < kRounds; r++) {
 		const int u = tid + r * kSplitNT;
@@ -555,6 +583,7 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 	return cur;
 	};
 	mark(0);
+	tr[0] += tr[8] + tr[9];
 	const int cur = half == 0 ? stages(std::integral_constant<int, 0>()) : stages(std::integral_constant<int, 1>());
 	mark(1);
 	const uint32_t* const fin = lds + cur * 4 * kPlane;
@@ -565,8 +594,8 @@ __global__ __launch_bounds__(kSplitNT, 1) void antt_bs3_pass(BsParams P) {
 	}
 	mark(3);
 	if (TR && lane == 0) {
-		unsigned long long* o = P.trace + ((size_t)blockIdx.x * (kSplitNT / 64) + w) * 8;
-		for (int i = 0; i < 8; i++) o[i] = tr[i];
+		unsigned long long* o = P.trace + ((size_t)blockIdx.x * (kSplitNT / 64) + w) * kTraceSlots;
+		for (int i = 0; i < kTraceSlots; i++) o[i] = tr[i];
 	}
 }
 
@@ -585,21 +614,35 @@ struct BsAt {
 };
 const void* bs_kernel_fn(int instance) { return instance_table<BsAt>(instance, std::make_index_sequence<kNttInstanceCount>()); }
 
-// BN_TRACE: the phase cycles the waves of one launch left in d_trace (8 words per wave, the slots of
-// tr[] in antt_bs_pass), as averages per wave-tile
-static int print_trace(int i, const NttLaunch& nl, int fmax, const unsigned long long* d_trace, size_t waves, hipStream_t st) {
-	std::vector<unsigned long long> h(waves * 8);
+// BN_TRACE: a zeroed device buffer of kTraceSlots words per wave for one launch
+int trace_buffer(size_t waves, hipStream_t st, unsigned long long** out) {
+	constexpr size_t kTraceBytes = (size_t)1 << 26;
+	static unsigned long long* trbuf = nullptr;
+	if (waves * kTraceSlots * sizeof(*trbuf) > kTraceBytes) BN_FAIL(BN_ERR_UNSUPPORTED, "BN_TRACE: %zu waves do not fit the trace buffer", waves);
+	if (!trbuf)
+		if (int rc = dev_alloc(&trbuf, kTraceBytes)) return rc;
+	BN_HIP(hipMemsetAsync(trbuf, 0, waves * kTraceSlots * sizeof(*trbuf), st));
+	*out = trbuf;
+	return BN_OK;
+}
+// BN_TRACE: the phase cycles the waves of one launch left in d_trace (kTraceSlots words per wave, the
+// slots of tr[] in antt_bs_pass), as averages per wave-tile. The load phase is split into issue (start
+// to last tile load issued), data (to tile data complete) and lds (to cu_w ready and the tile in LDS;
+// antt_rr_pass: the tile in registers); antt_rr_pass stamps only its load phase
+int print_trace(int i, const NttLaunch& nl, int fmax, const unsigned long long* d_trace, size_t waves, hipStream_t st) {
+	std::vector<unsigned long long> h(waves * kTraceSlots);
 	BN_HIP(hipStreamSynchronize(st));
 	BN_HIP(hipMemcpy(h.data(), d_trace, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost));
-	double acc[8] = {0};
+	double acc[kTraceSlots] = {0};
 	for (size_t w = 0; w < waves; w++)
-		for (int k = 0; k < 8; k++) acc[k] += (double)h[w * 8 + k];
+		for (int k = 0; k < kTraceSlots; k++) acc[k] += (double)h[w * kTraceSlots + k];
 	const double t = acc[4] > 0 ? acc[4] : 1;  // wave-tiles
+	const NttFamily f = kNttInstances[nl.instance].family;
 	fprintf(stderr,
-	        "trace pass %d (%s, fmax %d, %zu wave-tiles, cycles per wave-tile): load %.0f  block %.0f [pre %.0f mul %.0f post %.0f]  "
-	        "inword+tr %.0f  store %.0f\n",
-	        i, nl.threads == kSplitNT ? "split" : "tile", fmax, (size_t)acc[4], acc[0] / t, acc[1] / t, acc[5] / t, acc[6] / t,
-	        acc[7] / t, acc[2] / t, acc[3] / t);
+	        "trace pass %d (%s, fmax %d, %zu wave-tiles, cycles per wave-tile): load %.0f [issue %.0f data %.0f lds %.0f]  "
+	        "block %.0f [pre %.0f mul %.0f post %.0f]  inword+tr %.0f  store %.0f\n",
+	        i, f == NttFamily::Rr ? "reg" : f == NttFamily::Bs3 ? "split" : "tile", fmax, (size_t)acc[4], acc[0] / t, acc[8] / t,
+	        acc[9] / t, (acc[0] - acc[8] - acc[9]) / t, acc[1] / t, acc[5] / t, acc[6] / t, acc[7] / t, acc[2] / t, acc[3] / t);
 	return BN_OK;
 }
 
@@ -615,18 +658,13 @@ static int launch_one(bn_antt_plan* plan, int i, const uint32_t* d_in, uint32_t*
 	prm.log_h = plan->log_h;
 	prm.log_rate = plan->log_rate;
 	prm.dbg = kn.dbg;
+	prm.ts = plan->starts[i];
+	prm.ut = plan->ut_dev;
 	prm.p = pass;
 	prm.trace = nullptr;
 	const size_t waves = nl.grid * (nl.threads / 64);
-	if (kn.trace) {
-		constexpr size_t kTraceBytes = (size_t)1 << 26;
-		static unsigned long long* trbuf = nullptr;
-		if (waves * 8 * sizeof(*trbuf) > kTraceBytes) BN_FAIL(BN_ERR_UNSUPPORTED, "BN_TRACE: %zu waves do not fit the trace buffer", waves);
-		if (!trbuf)
-			if (int rc = dev_alloc(&trbuf, kTraceBytes)) return rc;
-		BN_HIP(hipMemsetAsync(trbuf, 0, waves * 8 * sizeof(*trbuf), st));
-		prm.trace = trbuf;
-	}
+	if (kn.trace)
+		if (int rc = trace_buffer(waves, st, &prm.trace)) return rc;
 	int rc = timing_begin(plan, i, st);
 	if (rc != BN_OK) return rc;
 	void* args[] = {&prm};

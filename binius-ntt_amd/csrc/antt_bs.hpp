@@ -33,6 +33,11 @@ int bs_time_passes(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, si
 const void* bs_pass_kernel(bn_antt_plan* plan, int i);
 // its inverse (antt_inv.hip): one coset block of evaluations back to coefficients
 int launch_inv_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, int coset, size_t batch, hipStream_t st);
+// BN_TRACE (development build, antt_bs.hip): the zeroed per-wave stamp buffer of a launch, and its
+// print-out as cycles per wave-tile
+constexpr int kTraceSlots = 10;
+int trace_buffer(size_t waves, hipStream_t st, unsigned long long** out);
+int print_trace(int i, const NttLaunch& nl, int fmax, const unsigned long long* d_trace, size_t waves, hipStream_t st);
 // pass i (timing kind) on register tiles (antt_rr.hip), as plan_pass decided
 int rr_launch_pass(bn_antt_plan* plan, int i, const NttLaunch& nl, const BsDevKnobs& kn, const uint32_t* d_in, uint32_t* d_out,
                    hipStream_t st);

@@ -1,8 +1,9 @@
 // Device helpers shared by the bitsliced kernels of the additive NTT: the forward LDS-tile passes
 // (antt_bs.hip), the inverse passes (antt_inv.hip) and the register-tile passes (antt_rr.hip). Every
 // piece of tile scaffolding has its one definition here: the tile's address bits, its twiddle tables,
-// the LDS image and the two HBM layouts. Helpers that read only the fields BsPass and RtPass share
-// (n_outer, ob, bb, two, twc) are templates on the pass table.
+// the LDS image and the two HBM layouts. Helpers that read only the field BsPass and RtPass share
+// (bb) are templates on the pass table; the start of a tile (its address bits and the uniform parts of
+// its twiddles) reads the pass's TileStart and the plan's chunk tables, not the pass table.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -52,17 +53,36 @@ struct TileAddr {
 	size_t batch;
 	size_t outer_off;  // the outer bits at their index positions (in blocks)
 };
-// (the inverse reads and writes one coset block: log_rate = 0, its coset is a launch parameter)
-template <class Pass>
-__device__ __forceinline__ TileAddr tile_addr(const Pass& ps, int log_rate) {
+// (the inverse reads and writes one coset block: log_rate = 0, its coset is a launch parameter).
+// Scalar shifts and ORs on the pass's TileStart (tile_outer_off), no table walk: nothing but the
+// kernel's arguments stands ahead of the tile's first load. ONE_RUN: the bottom pass's outer bits are
+// one run of index bits (plan_tile_starts checks it), a single shift. RUN_LOOP: see below
+template <bool ONE_RUN = false, bool RUN_LOOP = false>
+__device__ __forceinline__ TileAddr tile_addr(const TileStart& t, int log_rate) {
 	const size_t tile = blockIdx.x;
 	TileAddr a;
-	a.outer = tile & (((size_t)1 << ps.n_outer) - 1);
-	const size_t rest = tile >> ps.n_outer;
+	a.outer = tile & (((size_t)1 << t.n_outer) - 1);
+	const size_t rest = tile >> t.n_outer;
 	a.coset = (int)(rest & ((1u << log_rate) - 1));
 	a.batch = rest >> log_rate;
-	a.outer_off = 0;
-	for (int m = 0; m < ps.n_outer; m++) a.outer_off |= ((a.outer >> m) & 1) << ps.ob[m];
+	if (ONE_RUN) {
+		a.outer_off = a.outer << t.shift[0];
+	} else if (!RUN_LOOP) {
+		a.outer_off = tile_outer_off(t, a.outer);
+	} else {
+		// antt_rr_pass: tile_outer_off as a loop over the runs, both pairs in registers before it. With
+		// the straight code, and nothing else changed, its upper instances lose a wave of occupancy
+		// (<4, MID, 16>: 235 VGPRs against 168): the scheduler's occupancy target follows the block
+		// structure ahead of the tile's loads
+		uint32_t mask = t.mask[0], mask1 = t.mask[1];
+		int shift = t.shift[0], shift1 = t.shift[1];
+		a.outer_off = 0;
+#pragma unroll 1
+		for (int r = 0; r < t.n_runs; r++) {
+			a.outer_off |= (a.outer & mask) << shift;
+			mask = mask1, shift = shift1;
+		}
+	}
 	return a;
 }
 // tile block q -> its index bits
@@ -86,13 +106,36 @@ __device__ __forceinline__ size_t bitsliced_off(const Pass& ps, size_t outer_off
 }
 
 // ---- twiddles: linear in the index bits, tabulated per stage j of the pass.
-// Workgroup-uniform part (outer and coset bits); the tables are zero above the plan's log_rate
-template <class Pass>
-__device__ __forceinline__ uint32_t uniform_tw(const Pass& ps, int j, size_t outer, int coset, int rate_bits) {
-	uint32_t c = 0;
-	for (int m = 0; m < ps.n_outer; m++) c ^= ps.two[j][m] & (0u - (uint32_t)((outer >> m) & 1));
-	for (int b = 0; b < rate_bits; b++) c ^= ps.twc[j][b] & (0u - (uint32_t)((coset >> b) & 1));
-	return c;
+// Workgroup-uniform part (outer and coset bits) of every stage: the XOR of one row of the pass's
+// chunk tables per chunk of x = outer | coset << n_outer (TileStart, antt_passes.hpp). The row
+// addresses are wave-uniform and the tables never change after the plan is prepared, so the rows come
+// through the constant address space as scalar loads, all kMaxChunks of them in flight at once
+// behind one wait, and are XORed on the scalar unit (uniform_tw_rows: stage j's word in u[j]): no
+// vector-memory instruction, so the only vmcnt a tile's start waits on is its own data's. `ut` is the
+// plan's table buffer. uniform_tw_to_lanes hands stage j's word to lane j.
+typedef const uint32_t __attribute__((address_space(4))) * ConstWords;
+__device__ __forceinline__ void uniform_tw_rows(const TileStart& t, const uint32_t* ut, size_t outer, int coset, uint32_t* u) {
+	const uint32_t x = (uint32_t)outer | ((uint32_t)coset << t.n_outer);
+	const ConstWords tab = (ConstWords)(uintptr_t)(ut + t.ut_word);
+#pragma unroll
+	for (int j = 0; j < kMaxStages; j++) u[j] = 0;
+#pragma unroll
+	for (int c = 0; c < kMaxChunks; c++) {
+		const ConstWords row = tab + ((uint32_t)(c * kChunkRows) + ((x >> (kChunkBits * c)) & (kChunkRows - 1))) * kMaxStages;
+#pragma unroll
+		for (int j = 0; j < kMaxStages; j++) u[j] ^= row[j];
+	}
+}
+__device__ __forceinline__ uint32_t uniform_tw_to_lanes(const uint32_t* u) {
+	uint32_t v = 0;
+#pragma unroll
+	for (int j = 0; j < kMaxStages; j++) asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(u[j]), "n"(j));
+	return v;
+}
+__device__ __forceinline__ uint32_t uniform_tw_lanes(const TileStart& t, const uint32_t* ut, size_t outer, int coset) {
+	uint32_t u[kMaxStages];
+	uniform_tw_rows(t, ut, outer, coset, u);
+	return uniform_tw_to_lanes(u);
 }
 // part of tile block q
 __device__ __forceinline__ uint32_t tile_tw(const BsPass& ps, int j, int q) {

@@ -34,6 +34,8 @@ struct InvBsParams {
 	uint32_t* dst;
 	int log_h;
 	int coset;
+	TileStart ts;        // the pass's tile start and the plan's chunk tables (plan_tile_starts)
+	const uint32_t* ut;
 	BsPass p;
 };
 
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(64 * L, 2) void antt_inv_bs_pass(InvBsParams P) {
 	const size_t n = (size_t)1 << P.log_h;
 
 	// tile -> (outer bits, batch) -> addresses: one coset block in, one out
-	const TileAddr ta = tile_addr(ps, 0);
+	const TileAddr ta = tile_addr<IN_COMPACT>(P.ts, 0);
 	const size_t outer_off = ta.outer_off;
 	uint32_t* dst = P.dst + ta.batch * n * L;
 	const uint32_t* src = IN_COMPACT ? (P.src + ta.batch * n * L) : dst;
@@ -68,8 +70,11 @@ __global__ __launch_bounds__(64 * L, 2) void antt_inv_bs_pass(InvBsParams P) {
 		for (int r = 0; r < kLoads; r++) gbuf[r] = load_plane_bitsliced<L>(ps, src, outer_off, l, lane, r);
 	}
 
-	// workgroup-uniform twiddle part of every stage (outer bits + the coset), one lane per stage
-	if (lane < ps.k) cu_w[lane] = uniform_tw(ps, lane, ta.outer, P.coset, kMaxRateBits);
+	// workgroup-uniform twiddle part of every stage (outer bits + the coset), one lane per stage: scalar
+	// loads, behind the tile's loads in program order
+	__builtin_amdgcn_sched_barrier(0);
+	const uint32_t cuv = uniform_tw_lanes(P.ts, P.ut, ta.outer, P.coset);
+	if (lane < kMaxStages) cu_w[lane] = cuv;
 
 	// ---- tile into LDS
 	if (IN_COMPACT) {
@@ -215,6 +220,8 @@ int launch_inv_bs(bn_antt_plan* plan, const uint32_t* d_in, uint32_t* d_out, int
 		prm.dst = d_out;
 		prm.log_h = plan->log_h;
 		prm.coset = coset;
+		prm.ts = plan->starts[i];
+		prm.ut = plan->ut_dev;
 		prm.p = passes[i];
 		void* args[] = {&prm};
 		BN_HIP(hipLaunchKernel(inv_kernel_fn(nl.instance), dim3((unsigned)nl.grid), dim3(nl.threads), args, nl.lds, st));

@@ -214,6 +214,54 @@ static bool make_rt(const BsPass& p, bool bottom, RtPass* out) {
 	return true;
 }
 
+// ob[] of a pass as at most two runs of consecutive index bits (TileStart::mask / shift); false when
+// ob[] is anything else. The description is checked against ob[] bit by bit.
+static bool outer_runs(const BsPass& p, TileStart* t) {
+	int r0 = 0;  // length of the first run
+	while (r0 < p.n_outer && p.ob[r0] == p.ob[0] + r0) r0++;
+	t->n_outer = p.n_outer;
+	t->mask[0] = (uint32_t)(((uint64_t)1 << r0) - 1);
+	t->shift[0] = p.n_outer > 0 ? p.ob[0] : 0;
+	t->mask[1] = (uint32_t)(((uint64_t)1 << p.n_outer) - 1) & ~t->mask[0];
+	t->shift[1] = r0 < p.n_outer ? p.ob[r0] - r0 : 0;
+	t->n_runs = p.n_outer == 0 ? 0 : r0 < p.n_outer ? 2 : 1;
+	if (t->shift[0] < 0 || t->shift[1] < 0) return false;
+	for (int m = 0; m < p.n_outer; m++)
+		if (tile_outer_off(*t, (size_t)1 << m) != (size_t)1 << p.ob[m]) return false;
+	return true;
+}
+
+int plan_tile_starts(int log_rate, const std::vector<BsPass>& passes, std::vector<TileStart>& starts, std::vector<uint32_t>& ut) {
+	starts.assign(passes.size(), TileStart{});
+	ut.assign(passes.size() * kPassUtWords, 0u);
+	for (size_t i = 0; i < passes.size(); i++) {
+		const BsPass& p = passes[i];
+		TileStart& t = starts[i];
+		const bool bottom = p.role == ROLE_LAST || p.role == ROLE_SINGLE;
+		if (p.n_outer < 0 || p.n_outer > kMaxOuter || log_rate < 0 || log_rate > kMaxRateBits || !outer_runs(p, &t))
+			BN_FAIL(BN_ERR_UNSUPPORTED, "pass %zu: the outer bits are not two runs of index bits", i);
+		if (bottom && t.mask[1] != 0) BN_FAIL(BN_ERR_UNSUPPORTED, "bottom pass: the outer bits are not one run of index bits");
+		t.n_bits = p.n_outer + log_rate;
+		t.n_chunks = (t.n_bits + kChunkBits - 1) / kChunkBits;
+		if (t.n_chunks > kMaxChunks) BN_FAIL(BN_ERR_UNSUPPORTED, "pass %zu: %d outer and coset bits need more than %d chunks", i, t.n_bits, kMaxChunks);
+		t.ut_word = (uint32_t)(i * kPassUtWords);
+		// bit b of x = outer | coset << n_outer contributes two[j][b] or twc[j][b - n_outer]; each row by
+		// one XOR from the row without its lowest set bit
+		uint32_t* tab = ut.data() + t.ut_word;
+		for (int c = 0; c < t.n_chunks; c++)
+			for (int v = 1; v < kChunkRows; v++) {
+				const int low = __builtin_ctz((unsigned)v), b = c * kChunkBits + low;
+				uint32_t* row = tab + ((size_t)c * kChunkRows + v) * kMaxStages;
+				const uint32_t* rest = tab + ((size_t)c * kChunkRows + (v & (v - 1))) * kMaxStages;
+				for (int j = 0; j < kMaxStages; j++) {
+					const uint32_t bit = j >= p.k || b >= t.n_bits ? 0u : b < p.n_outer ? p.two[j][b] : p.twc[j][b - p.n_outer];
+					row[j] = rest[j] ^ bit;
+				}
+			}
+	}
+	return BN_OK;
+}
+
 int plan_pass_tables(int log_h, int log_rate, const std::vector<uint32_t>& s, std::vector<BsPass>& passes,
                      std::vector<RtPass>& rt) {
 	passes = plan_passes(log_h, log_rate, s);
@@ -222,6 +270,11 @@ int plan_pass_tables(int log_h, int log_rate, const std::vector<uint32_t>& s, st
 	for (size_t i = 0; i < passes.size(); i++) {
 		const bool bottom = passes[i].role == ROLE_LAST || passes[i].role == ROLE_SINGLE;
 		if (!make_rt(passes[i], bottom, &rt[i])) BN_FAIL(BN_ERR_UNSUPPORTED, "register-tile pass table: stage bits are not the top tile bits");
+		// the kernels place the outer bits with two masks and shifts (TileStart): a table they cannot
+		// describe fails the plan here, with the other table checks
+		TileStart t{};
+		if (!outer_runs(passes[i], &t) || (bottom && t.mask[1] != 0))
+			BN_FAIL(BN_ERR_UNSUPPORTED, "pass %zu: the outer bits are not the runs of index bits the kernels place", i);
 	}
 	return BN_OK;
 }

@@ -45,7 +45,9 @@ constexpr uint32_t lane_mask(int j) {
 }
 
 // One pass = k consecutive stages lo..lo+k-1 over every tile. Passed by value as a kernel
-// argument (~2.6 KB), so every table read is a scalar load from the kernarg segment.
+// argument (~2.6 KB), so every table read is a scalar load from the kernarg segment. No kernel reads
+// ob, two and twc any more (the tile's start comes from TileStart and the plan's chunk tables, below);
+// they stay for the planner, plan_tile_starts and the host-only exports.
 struct BsPass {
 	int lo, k, role, n_outer;
 	int bb[kBlkBits];                        // index bit of tile block bit m
@@ -80,6 +82,39 @@ struct RtPass {
 	uint32_t twc[kMaxStages][kMaxRateBits];
 	uint32_t pat[5][32];  // in-word stage s: bit-lane part of the twiddle words (R0/R1 difference folded)
 };
+
+// The start of a tile (every pass kernel): what a work-group needs of its tile index before it can
+// load the tile and run the stages, in a form that costs no serial table walk.
+//   * The outer bits ob[] of a pass are at most two contiguous runs of index bits, so the packed
+//     outer bits go to their index positions with two masks and shifts:
+//       outer_off = (outer & mask[0]) << shift[0] | (outer & mask[1]) << shift[1]
+//     (the bottom pass has one run: mask[1] = 0, and its kernels shift only).
+//   * The work-group-uniform twiddle part of stage j is linear in x = outer | coset << n_outer. x is
+//     cut into chunks of kChunkBits bits, and UT[c][v][j] holds the XOR of the two[j][.] / twc[j][.]
+//     contributions of the set bits of chunk c's value v: the uniform part is the XOR over the
+//     chunks of one row of kMaxStages words each. Chunks above n_chunks have the value 0, whose row is
+//     zero in every chunk; a pass's tables always hold kMaxChunks chunks, so a kernel reads
+//     kMaxChunks rows without a branch.
+constexpr int kChunkBits = 6;
+constexpr int kChunkRows = 1 << kChunkBits;
+constexpr int kMaxChunks = 4;  // a plan has log_h + log_rate <= 32: at most 20 outer and coset bits
+constexpr size_t kPassUtWords = (size_t)kMaxChunks * kChunkRows * kMaxStages;  // 12 KiB per pass
+struct TileStart {
+	uint32_t mask[2];
+	int shift[2];
+	int n_runs;                     // 0, 1 or 2: the pairs in use (a pair not in use has mask 0)
+	int n_outer, n_bits, n_chunks;  // n_bits = n_outer + log_rate, n_chunks = ceil(n_bits / kChunkBits)
+	uint32_t ut_word;               // first word of the pass's chunk tables in the plan's table buffer
+};
+// outer bits (packed) -> their index positions; what the kernels compute
+constexpr size_t tile_outer_off(const TileStart& t, size_t outer) {
+	return ((outer & t.mask[0]) << t.shift[0]) | ((outer & t.mask[1]) << t.shift[1]);
+}
+// The tile starts of a plan's passes and the chunk tables of all of them (`ut`, kPassUtWords words
+// per pass, in pass order: the plan copies it to the device once). BN_ERR_UNSUPPORTED when a pass's
+// outer bits are not two runs (checked bit by bit against ob[]), when the bottom pass has more than
+// one run, or when outer and coset bits need more than kMaxChunks chunks.
+int plan_tile_starts(int log_rate, const std::vector<BsPass>& passes, std::vector<TileStart>& starts, std::vector<uint32_t>& ut);
 
 // precompute_subspace_evals (src/ulvt/ntt/additive_ntt.cuh:273-309), GF(2^32) values: log_h rows of
 // width = log_h + log_rate - 1 columns, row-major.
@@ -149,7 +184,7 @@ constexpr bool valid_variant(int v) { return v == 0 || v == 1 || v == 4 || v == 
 // reads none and has the defaults. They measure or select among kernels the product itself launches:
 //   BN_DEBUG_FLAGS=bits  skip work for timing (wrong results): 1 no tile loads, 2 no tile stores,
 //                        4 no multiplies (antt_bs_pass; antt_rr_pass takes bits 1 and 2, antt_bs3_pass bit 2)
-//   BN_TRACE=1           per-wave phase times in cycles on stderr (antt_bs_pass, antt_bs3_pass)
+//   BN_TRACE=1           per-wave phase times in cycles on stderr (antt_bs_pass, antt_bs3_pass; antt_rr_pass: its load phase)
 //   BN_SPLIT=0/1         upper GF(2^16/32) passes never / always on the lane-split kernel
 //   BN_RR_LAST=0         small bottom passes stay on LDS tiles
 //   BN_ANTT_VARIANT=v    kernel variant of new plans with log_h >= 12 (1, 4 or 5)

@@ -24,6 +24,10 @@ struct bn_antt_plan {
 	// filled once by bs_prepare; empty for variant-0 plans
 	std::vector<bn::BsPass> passes;
 	std::vector<bn::RtPass> rt;
+	// the tile start of every pass and, on the device, the chunk tables of all of them
+	// (plan_tile_starts): written once by bs_prepare, read by every pass kernel, freed with the plan
+	std::vector<bn::TileStart> starts;
+	uint32_t* ut_dev = nullptr;
 	hipStream_t own_stream = nullptr;
 	// host-apply staging
 	void* h_dev_in = nullptr;

@@ -34,16 +34,21 @@ struct RrParams {
 	const uint32_t* src;
 	uint32_t* dst;
 	int log_h, log_rate;
+	TileStart ts;        // the pass's tile start and the plan's chunk tables (plan_tile_starts)
+	const uint32_t* ut;
 	RtPass p;
 #ifdef BN_DEV
 	int dbg;  // BN_DEBUG_FLAGS bit 0 = no tile loads, bit 1 = no tile stores (wrong results; timing
 	          // experiments on antt_rr_pass)
+	unsigned long long* trace;  // BN_TRACE=1: per-wave stamps of the load phase (print_trace, antt_bs.hip)
 #endif
 };
 #ifdef BN_DEV
 #define RR_DBG(P) ((P).dbg)
+#define RR_TRACE(P) ((P).trace != nullptr)
 #else
 #define RR_DBG(P) 0
+#define RR_TRACE(P) false
 #endif
 
 // ld_stream / st_stream on four consecutive registers
@@ -115,30 +120,35 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 	const int tid = threadIdx.x;
 	const int w = tid >> 6, lane = tid & 63;
 	const size_t n = (size_t)1 << P.log_h;
+	// BN_TRACE (development build): the load phase's stamps, as antt_bs_pass's
+	const bool TR = RR_TRACE(P);
+	auto ts = [&]() -> unsigned long long {
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		return __builtin_amdgcn_s_memtime();
+	};
+	[[maybe_unused]] const unsigned long long t0 = TR ? ts() : 0;
+	[[maybe_unused]] unsigned long long t_issue = 0, t_data = 0;
 
 	// tile -> (outer bits, coset, batch)
-	const TileAddr ta = tile_addr(ps, P.log_rate);
+	const TileAddr ta = tile_addr<false, true>(P.ts, P.log_rate);
 	const size_t ooff = ta.outer_off;
 	uint32_t* dst = P.dst + (((ta.batch << P.log_rate) + (size_t)ta.coset) * n) * L;
 	const uint32_t* src = IN_COMPACT ? (P.src + ta.batch * n * L) : dst;
-	// tile_off and uniform_tw of antt_bs_dev.hpp, written out: the GF(2^32)-element (L = 1) bottom-pass
-	// instances under the three-waves bound spill, and through the shared helpers (same arithmetic)
-	// their spill counts move (FMAX 16 / 32: 46 -> 24 and 130 -> 18 at ROLE_LAST, 60 -> 17 and
-	// 123 -> 125 at ROLE_SINGLE)
+	// tile_off of antt_bs_dev.hpp, written out: the GF(2^32)-element (L = 1) bottom-pass instances under
+	// the three-waves bound spill, and their spill counts move with the form of this helper
 	auto tile_off = [&](int q) -> size_t {
 		size_t off = 0;
 #pragma unroll
 		for (int m = 0; m < kBlkBits; m++) off |= (size_t)((q >> m) & 1) << ps.bb[m];
 		return off;
 	};
-	// work-group-uniform twiddle part (outer and coset bits) of stage j, held by lane j
-	uint32_t cuv = 0;
-	if (lane < ps.k) {
-		for (int m = 0; m < ps.n_outer; m++)
-			if ((ta.outer >> m) & 1) cuv ^= ps.two[lane][m];
-		for (int b = 0; b < P.log_rate; b++)
-			if ((ta.coset >> b) & 1) cuv ^= ps.twc[lane][b];
-	}
+	// work-group-uniform twiddle part (outer and coset bits) of stage j, held by lane j: four scalar row
+	// loads and no wait of their own. Written here, ahead of the tile's loads, the compiler sends the
+	// first row with the last kernel-argument load (bb[]) and the others between the tile's loads, and
+	// places the XORs and the lane writes behind them (profiles/ntt_tile_start_resusage.txt has the
+	// prologue). Written behind the tile's loads, antt_rr_pass<1, FIRST, 32> takes 231 VGPRs against
+	// 167 and loses a wave of occupancy
+	const uint32_t cuv = uniform_tw_lanes(P.ts, P.ut, ta.outer, ta.coset);
 	auto ucu = [&](int j) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)cuv, j); };
 
 	const int G = coords(lane);
@@ -162,6 +172,11 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 				else
 					ld4(src + (ooff | tile_off(s + 64 * h) | (size_t)e) * 4, gv[h][r]);
 			}
+		if (TR) {
+			t_issue = ts();
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			t_data = ts();
+		}
 #pragma unroll
 		for (int h = 0; h < 2; h++) {
 			if (h) __syncthreads();  // every wave has read the first half
@@ -198,7 +213,9 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 				__builtin_amdgcn_global_load_lds((const void*)(src + (ooff | tile_off(sl + 64 * h)) * L + 32 * w + 4 * c),
 				                                 (__attribute__((address_space(3))) void*)(wr + 1024 * r), 16, 0, 0);
 			}
+			if (TR && h) t_issue = ts();
 			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			if (TR && h) t_data = ts();
 			uint32_t* R = h ? R1 : R0;
 #pragma unroll
 			for (int c = 0; c < 8; c++) {
@@ -211,6 +228,15 @@ __global__ __launch_bounds__(64 * L, OCC) void antt_rr_pass(RrParams P) {
 			transpose32(R1);
 		}
 	}
+#ifdef BN_DEV
+	if (TR) {
+		const unsigned long long t_in = ts();
+		if (lane == 0) {
+			unsigned long long* o = P.trace + ((size_t)blockIdx.x * L + w) * kTraceSlots;
+			o[0] = t_in - t0, o[4] = 1, o[8] = t_issue - t0, o[9] = t_data - t_issue;
+		}
+	}
+#endif
 
 	// ---- block stages on tile bits 6 .. mlow (the bottom pass runs all seven)
 	const int mlow = LAST ? 0 : ps.mlow;
@@ -381,9 +407,15 @@ int rr_launch_pass(bn_antt_plan* plan, int i, const NttLaunch& nl, const BsDevKn
 	prm.dst = d_out;
 	prm.log_h = plan->log_h;
 	prm.log_rate = plan->log_rate;
+	prm.ts = plan->starts[i];
+	prm.ut = plan->ut_dev;
 	prm.p = plan->rt[i];
 #ifdef BN_DEV
 	prm.dbg = kn.dbg & 3;
+	prm.trace = nullptr;
+	const size_t waves = nl.grid * (nl.threads / 64);
+	if (kn.trace)
+		if (int rc = trace_buffer(waves, st, &prm.trace)) return rc;
 #else
 	(void)kn;
 #endif
@@ -391,7 +423,11 @@ int rr_launch_pass(bn_antt_plan* plan, int i, const NttLaunch& nl, const BsDevKn
 	if (rc != BN_OK) return rc;
 	void* args[] = {&prm};
 	BN_HIP(hipLaunchKernel(rr_kernel_fn(nl.instance), dim3((unsigned)nl.grid), dim3(nl.threads), args, nl.lds, st));
-	return timing_end(plan, i, st);
+	rc = timing_end(plan, i, st);
+#ifdef BN_DEV
+	if (rc == BN_OK && prm.trace) return print_trace(i, nl, pass_fmax(plan->passes[i]), prm.trace, waves, st);
+#endif
+	return rc;
 }
 
 }  // namespace bn
