@@ -82,6 +82,18 @@ public:
 		ulvt::bn_check(bn_antt_fri_fold_device(plan, d_in, d_out, round, arity, challenges, batch, stream));
 	}
 
+	// The verifier's fold of one opened leaf (host arithmetic: no device work, the plan gives only
+	// log_h and log_rate): element `index` of fri_fold(round, arity)'s output from the 2^arity input
+	// elements [index << arity, (index + 1) << arity) in `leaf`. Bit-exact with the device fold.
+	T fri_fold_leaf(int round, uint64_t index, const T* leaf, const uint32_t* challenges, int arity) const {
+		static_assert(sizeof(T) == 16 || sizeof(T) == 4, "GF(2^128) or GF(2^32) elements");
+		if (sizeof(T) != 16) throw ulvt::BnError(BN_ERR_UNSUPPORTED, "binius-ntt-amd: fri_fold_leaf is built for GF(2^128) plans");
+		T out{};
+		ulvt::bn_check(bn_antt_fri_fold_leaf(ntt_conf.log_h, ntt_conf.log_rate, round, arity, index, (const uint32_t*)leaf, challenges,
+		                                     (uint32_t*)&out));
+		return out;
+	}
+
 	// 0: compact tiles, per-butterfly twiddles (default for log_h < 12); 1: bitsliced LDS tiles;
 	// 4: bitsliced register tiles; 5: 4 for the GF(2^8)-twiddle passes, 1 for the others (default
 	// for log_h >= 12)

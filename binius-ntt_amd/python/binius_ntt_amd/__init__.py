@@ -65,6 +65,7 @@ def lib():
         "bn_antt_inverse_host": (i32, [vp, vp, sz, i32, vp]),
         "bn_antt_fri_fold_device": (i32, [vp, vp, vp, i32, i32, u32p, sz, vp]),
         "bn_antt_fri_fold_host": (i32, [vp, vp, sz, i32, i32, u32p, vp]),
+        "bn_antt_fri_fold_leaf": (i32, [i32, i32, i32, i32, ctypes.c_uint64, u32p, u32p, u32p]),
         "bn_antt_get_subspace_evals": (i32, [vp, u32p, sz]),
         "bn_antt_plan_query": (i32, [vp, i32, ctypes.POINTER(ctypes.c_int64)]),
         "bn_antt_plan_set_variant": (i32, [vp, i32]),
@@ -79,6 +80,9 @@ def lib():
         "bn_gf32_mul_device": (i32, [vp, vp, vp, sz, vp]),
         "bn_gf128_mul_repeat_device": (i32, [i32, vp, vp, sz, i32, vp]),
         "bn_bitslice_device": (i32, [vp, sz, i32, vp]),
+        "bn_bit_reverse_device": (i32, [vp, vp, i32, sz, i32, vp]),
+        "bn_bit_reverse_host": (i32, [i32, u32p, i32, i32, u32p]),
+        "bn_bit_reverse_device_split": (i32, [vp, vp, i32, sz, i32, i32, vp]),
         "bn_multiply_unrolled": (i32, [i32, u32p, u32p, u32p]),
         "bn_multiply_unrolled_device": (i32, [i32, vp, vp, vp, sz, vp]),
         "bn_circuit_device": (i32, [i32, vp, vp, vp, sz, vp]),
@@ -534,6 +538,53 @@ def bitslice(buf, untranspose=False, stream=None):
     _check_device_tensor(buf, buf.numel(), "buf")
     _check(lib().bn_bitslice_device(_ptr(buf), buf.numel() // 128, 1 if untranspose else 0,
                                     _stream(stream, _dev_index(buf))))
+
+
+def bit_reverse(inp, out, log_n, batch=1, bitsliced=False, stream=None, tile_log=0):
+    """bn_bit_reverse_device: out[b*2^n + rev_n(x)] = inp[b*2^n + x] for `batch` columns of 2^log_n
+    compact GF(2^128) elements in device tensors (4 * batch * 2^log_n words each); bitsliced: the
+    result in the layout of bitslice(), a data_is_transposed sumcheck column. `inp` is not written and
+    must not overlap `out`. Async on `stream` (default: torch's current stream of inp's device).
+    tile_log != 0 forces the tile's run length (bn_bit_reverse_device_split, a test hook)."""
+    if 0 <= log_n <= 30 and 0 < batch <= (1 << 32) >> log_n:  # else: the library's own error
+        _check_device_tensor(inp, (4 * batch) << log_n, "inp")
+        _check_device_tensor(out, (4 * batch) << log_n, "out")
+    st = _stream(stream, _dev_index(inp))
+    if tile_log:
+        _check(lib().bn_bit_reverse_device_split(_ptr(inp), _ptr(out), log_n, batch, 1 if bitsliced else 0, tile_log, st))
+    else:
+        _check(lib().bn_bit_reverse_device(_ptr(inp), _ptr(out), log_n, batch, 1 if bitsliced else 0, st))
+
+
+def bit_reverse_host(inp, bitsliced=False, device=0):
+    """bn_bit_reverse_host: the permutation of a (2^n, 4) uint32 host array as a new array of that
+    shape (bitsliced: the blocks' words in that shape), synchronous. n is taken from the size."""
+    a = np.ascontiguousarray(inp, dtype=np.uint32).reshape(-1, 4)
+    n = a.shape[0]
+    if n == 0 or n & (n - 1):
+        raise ValueError("inp must hold a power of two of elements")
+    out = np.zeros_like(a)
+    _check(lib().bn_bit_reverse_host(device, _u32p(a), n.bit_length() - 1, 1 if bitsliced else 0, _u32p(out)))
+    return out
+
+
+def fri_fold_leaf(log_h, log_rate, round, index, leaf, challenges):
+    """bn_antt_fri_fold_leaf: element `index` of the fold of rounds round .. round+arity-1 of a
+    (log_h, log_rate) GF(2^128) codeword, from the 2^arity elements of its leaf ((2^arity, 4) uint32,
+    or the leaf's bytes) and the (arity, 4) uint32 `challenges`. Host arithmetic: no plan, no device."""
+    ch = np.ascontiguousarray(challenges, dtype=np.uint32)
+    if ch.ndim != 2 or ch.shape[1] != 4:
+        raise ValueError("challenges must be an (arity, 4) uint32 array")
+    lf = np.frombuffer(bytes(leaf), dtype=np.uint32) if isinstance(leaf, (bytes, bytearray)) else np.ascontiguousarray(leaf, dtype=np.uint32).reshape(-1)
+    if 1 <= len(ch) <= 8 and lf.size != 4 << len(ch):
+        raise ValueError("the leaf holds %d words, need %d" % (lf.size, 4 << len(ch)))
+    lf = np.ascontiguousarray(lf)
+    out = np.zeros(4, np.uint32)
+    if index < 0:
+        raise ValueError("index must be >= 0")
+    _check(lib().bn_antt_fri_fold_leaf(log_h, log_rate, round, len(ch), index, _u32p(lf), _u32p(ch) if len(ch) else None,
+                                       _u32p(out)))
+    return out
 
 
 def multiply_unrolled(height, a, b, dst=None):

@@ -114,6 +114,17 @@ int bn_antt_fri_fold_device(bn_antt_plan* plan, const void* d_in, void* d_out, i
  * effect otherwise); `out` receives 2^(log_h+log_rate-round-arity) elements. */
 int bn_antt_fri_fold_host(bn_antt_plan* plan, const void* in, size_t in_elems, int round, int arity,
                           const uint32_t* challenges, void* out);
+/* The verifier's fold of one opened leaf (host only: no plan, no device).
+ * out = element `index` of the output of bn_antt_fri_fold_device(round, arity) for a (log_h, log_rate)
+ * GF(2^128) plan, computed from the 2^arity input elements [index << arity, (index+1) << arity) in
+ * `leaf` (the leaf bn_merkle_open_device returns for that index at log_leaf_elems = arity) and the
+ * arity challenges. Level l pairs leaf elements 2p, 2p+1 by the per-pair rule with the twiddle of
+ * stage round+l at the global pair index (index << (arity-1-l)) | p (low log_h+log_rate-1-round-l
+ * bits). Host arithmetic; bit-exact with the device fold. The subspace table is kept per thread
+ * while (log_h, log_rate) repeats. BN_ERR_INVALID: NULL pointer, parameters
+ * outside bn_antt_plan_create's / the fold's ranges, index >= 2^(log_h+log_rate-round-arity). */
+int bn_antt_fri_fold_leaf(int log_h, int log_rate, int round, int arity, uint64_t index,
+                          const uint32_t* leaf, const uint32_t* challenges, uint32_t* out);
 
 /* Copies the plan's normalised subspace-evaluation table s[i][j] (GF(2^32) values,
  * log_h rows x (log_h+log_rate-1) columns, row-major) to host memory. */
@@ -201,6 +212,32 @@ int bn_gf128_mul_repeat_device(int kind, void* d_state, const void* d_operand, s
 /* In-place compact -> bitsliced (untranspose == 0) or bitsliced -> compact (untranspose != 0)
  * over n_blocks 128-word blocks. Replaces transpose_kernel / untranspose_kernel. */
 int bn_bitslice_device(void* d_buf, size_t n_blocks, int untranspose, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Bit-reversal permutation of a device-resident GF(2^128) column (no reference counterpart): the
+ * data movement that lets the sumcheck (highest variable first) and the FRI fold (lowest index bit
+ * first) bind the variables in the same order
+ * ------------------------------------------------------------------------------------ */
+/* out[b*2^n + rev_n(x)] = in[b*2^n + x], x < 2^n, b < batch: compact GF(2^128) elements (16 B),
+ * rev_n = the n-bit reversal of the index. bitsliced != 0: each transform's output is then in the
+ * layout of bn_bitslice_device (needs log_n >= 5), i.e. the call equals the compact call followed
+ * by bn_bitslice_device on d_out; the buffer is a data_is_transposed sumcheck column as it is.
+ * The index is split hi (6 bits) | mid | lo (6 bits): a work-group moves the 2^12 elements of one
+ * value of mid through LDS, reading 64 runs of 1 KiB and writing 64 runs of 1 KiB, so every global
+ * access is whole 128-byte lines (log_n <= 1 is one device-to-device copy).
+ * d_in is not written; d_in and d_out must not overlap. Allocates nothing, asynchronous on
+ * `stream`, current device, all indexing 64-bit. 0 <= log_n <= 30. BN_ERR_INVALID with nothing
+ * launched: NULL or misaligned (16 B) buffer, log_n out of range, bitsliced with log_n < 5,
+ * batch == 0 or batch*2^log_n > 2^32 elements, overlapping ranges. */
+int bn_bit_reverse_device(const void* d_in, void* d_out, int log_n, size_t batch, int bitsliced, void* stream);
+/* The same on one transform in host memory (2^log_n x 4 words each way), synchronous, staged through
+ * a buffer on `device` that lives for the call. */
+int bn_bit_reverse_host(int device, const uint32_t* in, int log_n, int bitsliced, uint32_t* out);
+/* Test hook: the same with the tile's run length forced to 2^tile_log elements, 1..6 (0: default;
+ * other values BN_ERR_INVALID), so that multi-tile plans run at 2^4 .. 2^13 elements. Results are
+ * identical. */
+int bn_bit_reverse_device_split(const void* d_in, void* d_out, int log_n, size_t batch, int bitsliced,
+                                int tile_log, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Field primitives beside the hot path (src/ulvt/finite_fields)

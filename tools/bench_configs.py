@@ -37,6 +37,12 @@ merkle (only with --only merkle) SHA-256 Merkle commitment of the fold line's co
     for), a device-to-device copy of the same 256 MiB, and the six commits of the 4+4+4+4+4+2
     schedule next to its six folds, all in one process; ms, leaves/s, compressions/s, the share of
     the HBM peak and the share of the v_bitop3 issue ceiling from the static VALU count per compression.
+bitrev (only with --only bitrev) bit-reversal permutation of a GF(2^128) column, 2^24 and 2^20 elements,
+    compact and bitsliced (at 2^24 next to the compact call + bn_bitslice_device in alternating pairs),
+    with a device-to-device copy of the same bytes timed first and last in the same process (the
+    smaller reading counts: the yardstick DESIGN.md section 5.10 states the bound for).
+pcs (only with --only pcs) wall time of fri_pcs.prove_eval at log_h 20, log_rate 2, schedule 4+4+4+4+4,
+    32 queries, with its split into sumcheck, folds, commits and opens. For the record: no bound.
 Every line is one JSON object.
 """
 import argparse
@@ -249,6 +255,71 @@ def eq_line(dev, out, n, bitsliced_too, reps=30):
                  "over_fill": ms_eq / ms_fill, "hbm_peak_fraction": (16 << n) / (ms_eq * 1e-3) / HBM_PEAK,
                  "hbm_peak_bytes_per_s": HBM_PEAK})
     out(line)
+
+
+def bitrev_line(dev, out, n, pairs_too, reps=30):
+    """The bit-reversal permutation at 2^n elements: the compact and the bitsliced call (and, if asked,
+    the bitsliced call next to the compact call followed by bn_bitslice_device, in alternating pairs),
+    with a device-to-device copy of the same 2^n x 16 B timed first and last as the yardstick (the
+    smaller reading counts), all in one process; ms per call, device events after a warm-up call."""
+    import torch
+    import binius_ntt_amd as B
+    st = torch.cuda.current_stream(dev)
+    a = torch.randint(-2**31, 2**31, (4 << n,), dtype=torch.int32, device=dev)
+    o = torch.empty(4 << n, dtype=torch.int32, device=dev)
+
+    def then_bitslice():
+        B.bit_reverse(a, o, n, stream=st)
+        B.bitslice(o, stream=st)
+
+    ms_copy = [ev_time(lambda: o.copy_(a), reps, st)]
+    ms = ev_time(lambda: B.bit_reverse(a, o, n, stream=st), reps, st)
+    ms_bs = ev_time(lambda: B.bit_reverse(a, o, n, bitsliced=True, stream=st), reps, st)
+    line = {"config": "bitrev", "workload": "bit-reversal permutation of 2^%d GF(2^128) elements" % n,
+            "kernel": "bn::bit_reverse_tiles", "value": (1 << n) / (ms * 1e-3), "unit": "elements/s", "ms": ms,
+            "ms_bitsliced": ms_bs}
+    if pairs_too:
+        line["ms_bitsliced_vs_compact_then_bitslice"] = [
+            (ev_time(lambda: B.bit_reverse(a, o, n, bitsliced=True, stream=st), reps, st), ev_time(then_bitslice, reps, st))
+            for _ in range(3)]
+    ms_copy.append(ev_time(lambda: o.copy_(a), reps, st))
+    cp = min(ms_copy)
+    line.update({"ms_copy": ms_copy, "over_copy": ms / cp, "hbm_peak_fraction": (32 << n) / (ms * 1e-3) / HBM_PEAK,
+                 "hbm_peak_fraction_copy": (32 << n) / (cp * 1e-3) / HBM_PEAK, "hbm_peak_bytes_per_s": HBM_PEAK})
+    if pairs_too:
+        line["bound_over_copy"] = 1.5
+    out(line)
+
+
+def pcs_line(dev, out, log_h=20, log_rate=2, schedule=(4, 4, 4, 4, 4), n_queries=32, runs=3):
+    """Wall time of the opening proof (fri_pcs.prove_eval) of a committed 2^log_h-coefficient
+    polynomial and its split, the best of `runs` after a warm-up proof; commit and verify_eval once."""
+    import torch
+    import binius_ntt_amd as B
+    from binius_ntt_amd import fri_pcs
+    g = np.random.default_rng(13)
+    ntt = B.AdditiveNTT(B.AdditiveNTTConf(log_h, log_rate, B.FanPaarTowerField(7), device=dev.index or 0))
+    x = torch.randint(-2**31, 2**31, (4 << log_h,), dtype=torch.int32, device=dev)
+    z = g.integers(0, 2**32, size=(log_h, 4), dtype=np.uint64).astype(np.uint32)
+    t0 = time.perf_counter()
+    com, state = fri_pcs.commit(ntt, x, list(schedule))
+    torch.cuda.synchronize()
+    s_commit = time.perf_counter() - t0
+    best = None
+    for _ in range(runs + 1):
+        t0 = time.perf_counter()
+        proof = fri_pcs.prove_eval(state, z, n_queries, fri_pcs.Transcript(b"bench"))
+        torch.cuda.synchronize()
+        s = time.perf_counter() - t0
+        if best is None or s < best[0]:
+            best = (s, dict(state.timing))
+    t0 = time.perf_counter()
+    ok = fri_pcs.verify_eval(log_h, log_rate, list(schedule), com.root, z, proof.v, proof, n_queries, fri_pcs.Transcript(b"bench"))
+    s_verify = time.perf_counter() - t0
+    out({"config": "pcs", "workload": "FRI-Binius opening proof, log_h %d, log_rate %d, schedule %s, %d queries"
+         % (log_h, log_rate, "+".join(str(a) for a in schedule), n_queries), "value": best[0] * 1e3, "unit": "ms per prove_eval (wall)",
+         "ms_split": {k: v * 1e3 for k, v in best[1].items()}, "ms_commit": s_commit * 1e3, "ms_verify_host": s_verify * 1e3,
+         "accepted": bool(ok)})
 
 
 BITOP3_CEILING = 8.36e11    # wave-instructions/s chip-wide (DESIGN.md section 5.3)
@@ -533,6 +604,11 @@ def main():
         eq_line(dev, out, 20, False)
     if "merkle" in only:
         merkle_line(dev, out)
+    if "bitrev" in only:
+        bitrev_line(dev, out, 24, True)
+        bitrev_line(dev, out, 20, False)
+    if "pcs" in only:
+        pcs_line(dev, out)
     if a.out:
         with open(a.out, "w") as f:
             for d in lines:
