@@ -114,6 +114,15 @@ def lib():
         "bn_eq_eval": (i32, [i32, u32p, u32p, u32p]),
         "bn_eq_expand_device_split": (i32, [i32, u32p, u32p, vp, i32, i32, vp]),
         "bn_eq_expand_passes": (i32, [i32, i32, ctypes.POINTER(ctypes.c_int32), sz, ctypes.POINTER(i32)]),
+        "bn_rs_partial_evals_device": (i32, [vp, vp, i32, vp, vp]),
+        "bn_rs_partial_evals_host": (i32, [i32, u32p, u32p, i32, u32p]),
+        "bn_rs_partial_evals_device_split": (i32, [vp, vp, i32, vp, sz, vp]),
+        "bn_gf128_linear_map_device": (i32, [vp, vp, sz, u32p, i32, vp]),
+        "bn_gf128_linear_map_host": (i32, [i32, u32p, sz, u32p, i32, u32p]),
+        "bn_rs_batch_table": (i32, [u32p, u32p]),
+        "bn_rs_row_check": (i32, [u32p, u32p, u32p]),
+        "bn_rs_sumcheck_claim": (i32, [u32p, u32p, u32p]),
+        "bn_rs_eq_eval": (i32, [i32, u32p, u32p, u32p, u32p]),
         "bn_merkle_tree_digests": (i32, [i32, ctypes.POINTER(sz)]),
         "bn_merkle_open_bytes": (i32, [i32, i32, ctypes.POINTER(sz)]),
         "bn_merkle_row_offset": (i32, [i32, i32, ctypes.POINTER(sz)]),
@@ -878,6 +887,110 @@ def eq_expand_passes(num_vars, max_levels=0):
     n = ctypes.c_int()
     _check(lib().bn_eq_expand_passes(num_vars, max_levels, levels, 32, ctypes.byref(n)))
     return [levels[i] for i in range(n.value)]
+
+
+# ------------------------------------------------------------------ ring-switching (GF(2) witnesses)
+def _rs_words(a, rows, what):
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    if a.size != 4 * rows:
+        raise ValueError("%s must hold %d x 4 uint32 words (got %d words)" % (what, rows, a.size))
+    return a.reshape(rows, 4)
+
+
+def rs_partial_evals(packed, eq, log_n, out, stream=None, max_blocks_per_group=0):
+    """bn_rs_partial_evals_device: s^_v = XOR over w with bit_v(packed[w]) = 1 of eq[w], v = 0 .. 127, for
+    two bitsliced columns of 2^log_n elements in device tensors (4 * 2^log_n words each, the same element
+    order) into the device tensor `out` (512 words: 128 compact elements; need not be initialised). Async
+    on `stream` (default: torch's current stream of packed's device). max_blocks_per_group != 0 caps a
+    work-group's run of blocks (bn_rs_partial_evals_device_split, a test hook)."""
+    if 5 <= log_n <= 30:  # else: the library's own error
+        _check_device_tensor(packed, 4 << log_n, "packed")
+        _check_device_tensor(eq, 4 << log_n, "eq")
+    _check_device_tensor(out, 512, "out")
+    st = _stream(stream, _dev_index(packed))
+    if max_blocks_per_group:
+        _check(lib().bn_rs_partial_evals_device_split(_ptr(packed), _ptr(eq), log_n, _ptr(out), max_blocks_per_group, st))
+    else:
+        _check(lib().bn_rs_partial_evals_device(_ptr(packed), _ptr(eq), log_n, _ptr(out), st))
+
+
+def rs_partial_evals_host(packed, eq, device=0):
+    """bn_rs_partial_evals_host: the same on two (2^n, 4) uint32 host arrays holding bitsliced blocks,
+    as a new (128, 4) array, synchronous. n is taken from the size."""
+    a = np.ascontiguousarray(packed, dtype=np.uint32).reshape(-1, 4)
+    b = np.ascontiguousarray(eq, dtype=np.uint32).reshape(-1, 4)
+    n = a.shape[0]
+    if n == 0 or n & (n - 1) or b.shape != a.shape:
+        raise ValueError("the columns must hold the same power of two of elements")
+    out = np.zeros((128, 4), np.uint32)
+    _check(lib().bn_rs_partial_evals_host(device, _u32p(a), _u32p(b), n.bit_length() - 1, _u32p(out)))
+    return out
+
+
+def gf128_linear_map(inp, out, matrix, bitsliced=False, stream=None):
+    """bn_gf128_linear_map_device: out[w] = XOR over u with bit_u(inp[w]) = 1 of matrix[u] over the whole
+    device tensor `inp` (compact 4-word elements, or bitsliced 128-word blocks); `matrix` is a (128, 4)
+    uint32 host array. `out` may be `inp`. Async on `stream` (default: torch's current stream of inp's
+    device)."""
+    m = _rs_words(matrix, 128, "matrix")
+    _same_size("gf128_linear_map", inp, out)
+    words = inp.numel() * inp.element_size() // 4
+    unit = 128 if bitsliced else 4
+    if words % unit:
+        raise ValueError("inp must hold whole %s" % ("128-word blocks" if bitsliced else "elements"))
+    _check_device_tensor(inp, words, "inp")
+    _check_device_tensor(out, words, "out")
+    _check(lib().bn_gf128_linear_map_device(_ptr(inp), _ptr(out), words // unit, _u32p(m), 1 if bitsliced else 0,
+                                            _stream(stream, _dev_index(inp))))
+
+
+def gf128_linear_map_host(inp, matrix, bitsliced=False, device=0):
+    """bn_gf128_linear_map_host: the same on an (n, 4) uint32 host array as a new array, synchronous."""
+    a = np.ascontiguousarray(inp, dtype=np.uint32).reshape(-1, 4)
+    m = _rs_words(matrix, 128, "matrix")
+    if bitsliced and a.shape[0] % 32:
+        raise ValueError("bitsliced input must hold whole 32-element blocks")
+    out = np.zeros_like(a)
+    _check(lib().bn_gf128_linear_map_host(device, _u32p(a), a.shape[0] // 32 if bitsliced else a.shape[0], _u32p(m),
+                                          1 if bitsliced else 0, _u32p(out)))
+    return out
+
+
+def rs_batch_table(r2):
+    """bn_rs_batch_table: B[u] = eq(r'', u) as a (128, 4) uint32 array; r2 is (7, 4). Host arithmetic."""
+    r2 = _rs_words(r2, 7, "r2")
+    out = np.zeros((128, 4), np.uint32)
+    _check(lib().bn_rs_batch_table(_u32p(r2), _u32p(out)))
+    return out
+
+
+def rs_row_check(shat, r_low):
+    """bn_rs_row_check: sum_v eq(r_low, v) s^_v; shat is (128, 4), r_low (7, 4). Host arithmetic."""
+    shat, r_low = _rs_words(shat, 128, "shat"), _rs_words(r_low, 7, "r_low")
+    out = np.zeros(4, np.uint32)
+    _check(lib().bn_rs_row_check(_u32p(shat), _u32p(r_low), _u32p(out)))
+    return out
+
+
+def rs_sumcheck_claim(shat, r2):
+    """bn_rs_sumcheck_claim: s_0 = sum_u B[u] s^row_u, the rows of s^ as a bit matrix. Host arithmetic."""
+    shat, r2 = _rs_words(shat, 128, "shat"), _rs_words(r2, 7, "r2")
+    out = np.zeros(4, np.uint32)
+    _check(lib().bn_rs_sumcheck_claim(_u32p(shat), _u32p(r2), _u32p(out)))
+    return out
+
+
+def rs_eq_eval(r_high, rho, r2):
+    """bn_rs_eq_eval: A~(rho), the mapped eq column of r_high at the sumcheck's challenges; r_high and
+    rho are (n, 4), r2 (7, 4). Host arithmetic."""
+    a = np.ascontiguousarray(r_high, dtype=np.uint32).reshape(-1, 4)
+    b = np.ascontiguousarray(rho, dtype=np.uint32).reshape(-1, 4)
+    if a.shape != b.shape:
+        raise ValueError("the points differ in length")
+    r2 = _rs_words(r2, 7, "r2")
+    out = np.zeros(4, np.uint32)
+    _check(lib().bn_rs_eq_eval(a.shape[0], _u32p(a) if len(a) else None, _u32p(b) if len(b) else None, _u32p(r2), _u32p(out)))
+    return out
 
 
 # ------------------------------------------------------------------ SHA-256 Merkle commitment

@@ -417,6 +417,64 @@ int bn_eq_expand_device_split(int num_vars, const uint32_t* challenges, const ui
 int bn_eq_expand_passes(int num_vars, int max_levels, int32_t* levels, size_t cap, int* n_passes);
 
 /* ------------------------------------------------------------------------------------
+ * Ring-switching for GF(2) witnesses (no reference counterpart; Diamond-Posen, "Polylogarithmic Proofs
+ * for Multilinears over Binary Towers", section 4): the reduction from "t(r) = s", t a multilinear with
+ * 2^l bits and r in GF(2^128)^l, to a sumcheck over the packed column t'[w] = sum_v t[128 w + v] beta_v
+ * (2^(l-7) elements) that the FRI-Binius opening finishes. beta_v is the element whose only set bit is
+ * bit v: bit v % 32 of word v / 32. With r_low = r[0:7], r_high = r[7:l] and E[w] = eq(r_high, w)
+ * (r_high,j pairs with bit j of w):
+ *   partial evaluations  s^_v = XOR over w with bit_v(t'[w]) = 1 of E[w], v = 0 .. 127
+ *   row check            s == sum_v eq(r_low, v) s^_v                    (r_low,i pairs with bit i of v)
+ *   batching             B[u] = eq(r'', u), r'' in GF(2^128)^7           (r''_i pairs with bit i of u)
+ *   sumcheck claim       s_0 = sum_u B[u] s^row_u, s^row_u = sum_v bit_u(s^_v) beta_v
+ *   sumcheck column      A[w] = XOR over u with bit_u(E[w]) = 1 of B[u]; sum_w A[w] t'[w] = s_0
+ *   last claim           A~(rho) = sum_u B[u] e_u, e = prod_j (1 (x) (1 ^ rho_j) + r_high,j (x) 1)
+ * Every result is bit-exact.
+ * ------------------------------------------------------------------------------------ */
+/* The partial evaluations of two bitsliced columns of 2^log_n elements (128-word blocks, the layout of
+ * bn_bitslice_device and of a data_is_transposed sumcheck column), both in the same element order:
+ * d_out receives 128 compact elements (2 KiB; it need not be initialised, the call zeroes it on
+ * `stream`). Per block a GF(2) matrix product acc[v][u] ^= T[v] & E[u] (16 384 lane-operations per 32
+ * elements); work-groups of eight waves take contiguous runs of blocks and combine with atomicXor.
+ * Neither input is written. Allocates nothing, asynchronous on `stream`, current device, all indexing
+ * 64-bit. 5 <= log_n <= 30. BN_ERR_INVALID with nothing launched: NULL or misaligned (16 B) buffer,
+ * log_n out of range, d_out inside an input. */
+int bn_rs_partial_evals_device(const void* d_packed, const void* d_eq, int log_n, void* d_out, void* stream);
+/* The same on host memory (2^log_n x 4 words per column, bitsliced blocks; out: 128 x 4 words),
+ * synchronous, staged through a buffer on `device` that lives for the call. */
+int bn_rs_partial_evals_host(int device, const uint32_t* packed, const uint32_t* eq, int log_n, uint32_t* out);
+/* Test hook: the same with at most max_blocks_per_group blocks per work-group (0: the default), so
+ * that several work-groups, the last one short, reduce into one result at 2^6 .. 2^13 elements.
+ * Results are identical. */
+int bn_rs_partial_evals_device_split(const void* d_packed, const void* d_eq, int log_n, void* d_out,
+                                     size_t max_blocks_per_group, void* stream);
+/* A GF(2)-linear map of GF(2^128) applied to every element: out[w] = XOR over u with bit_u(in[w]) = 1
+ * of matrix[u]. `matrix` is 128 x 4 words of host memory, read before the call returns (passed to the
+ * kernel by value). bitsliced == 0: n >= 1 compact elements. bitsliced != 0: n 128-word blocks, in and
+ * out in the layout of bn_bitslice_device. In place (d_out == d_in) is allowed; any other overlap is
+ * rejected. The compact kernel looks every byte of the element up in one of 16 tables of 256 entries
+ * in LDS (64 KiB, built per work-group); bitsliced blocks run it between the two bit transposes, in
+ * place in d_out. Allocates nothing, asynchronous on `stream`, current device. BN_ERR_INVALID with
+ * nothing launched: NULL argument, misaligned (16 B) buffer, n == 0 or above 2^32 elements,
+ * partially overlapping ranges. */
+int bn_gf128_linear_map_device(const void* d_in, void* d_out, size_t n, const uint32_t* matrix, int bitsliced,
+                               void* stream);
+/* The same on host memory, synchronous, staged through a buffer on `device` that lives for the call. */
+int bn_gf128_linear_map_host(int device, const uint32_t* in, size_t n, const uint32_t* matrix, int bitsliced,
+                             uint32_t* out);
+/* The verifier's arithmetic (host only: no plan, no device).
+ * bn_rs_batch_table: out[u] = B[u], 128 x 4 words, from r2 = r'' (7 x 4 words); also the `matrix` the
+ * prover passes to bn_gf128_linear_map_device. */
+int bn_rs_batch_table(const uint32_t* r2, uint32_t* out);
+/* out = sum_v eq(r_low, v) s^_v: the right-hand side of the row check. shat 128 x 4, r_low 7 x 4. */
+int bn_rs_row_check(const uint32_t* shat, const uint32_t* r_low, uint32_t* out);
+/* out = s_0, the sumcheck's claim, from s^ and r''. */
+int bn_rs_sumcheck_claim(const uint32_t* shat, const uint32_t* r2, uint32_t* out);
+/* out = A~(rho): 256 products and one 128 x 128 bit-matrix application per variable. r_high and rho are
+ * n x 4 words (NULL allowed for n == 0), 0 <= n <= 121. */
+int bn_rs_eq_eval(int n, const uint32_t* r_high, const uint32_t* rho, const uint32_t* r2, uint32_t* out);
+
+/* ------------------------------------------------------------------------------------
  * SHA-256 Merkle commitment of a device-resident GF(2^128) codeword and its query openings (no
  * reference counterpart): the step between bn_antt_forward_device and bn_antt_fri_fold_device, and
  * between one fold and the next. Every result is bit-exact.

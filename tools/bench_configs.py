@@ -43,6 +43,12 @@ bitrev (only with --only bitrev) bit-reversal permutation of a GF(2^128) column,
     smaller reading counts: the yardstick DESIGN.md section 5.10 states the bound for).
 pcs (only with --only pcs) wall time of fri_pcs.prove_eval at log_h 20, log_rate 2, schedule 4+4+4+4+4,
     32 queries, with its split into sumcheck, folds, commits and opens. For the record: no bound.
+rs  (only with --only rs) the two ring-switching kernels (bn_rs_partial_evals_device on bitsliced columns,
+    bn_gf128_linear_map_device compact and bitsliced in place) at 2^24 and 2^20 packed elements, next
+    to bn_gf128_mul_device and bn_eq_expand_device on as many elements and a device copy of the same
+    bytes, all in one process; then fri_pcs.prove_eval_packed at n = 20 (2^27 bits), log_rate 2, schedule
+    4+4+4+4+4, 32 queries, next to prove_eval at the same shape, with the share of the ring-switching
+    steps in the whole opening. For the record: no bound.
 Every line is one JSON object.
 """
 import argparse
@@ -319,6 +325,76 @@ def pcs_line(dev, out, log_h=20, log_rate=2, schedule=(4, 4, 4, 4, 4), n_queries
     out({"config": "pcs", "workload": "FRI-Binius opening proof, log_h %d, log_rate %d, schedule %s, %d queries"
          % (log_h, log_rate, "+".join(str(a) for a in schedule), n_queries), "value": best[0] * 1e3, "unit": "ms per prove_eval (wall)",
          "ms_split": {k: v * 1e3 for k, v in best[1].items()}, "ms_commit": s_commit * 1e3, "ms_verify_host": s_verify * 1e3,
+         "accepted": bool(ok)})
+
+
+def rs_line(dev, out, n, reps=30):
+    """The two ring-switching kernels on 2^n packed elements: the partial evaluations of two bitsliced
+    columns and the linear map (compact, and bitsliced in place), next to bn_gf128_mul_device and
+    bn_eq_expand_device on as many elements and a device copy of the same 2^n x 16 B (timed first and
+    last, the smaller reading counts), all in one process; ms per call, device events after a warm-up
+    call."""
+    import torch
+    import binius_ntt_amd as B
+    st = torch.cuda.current_stream(dev)
+    g = np.random.default_rng(17)
+    a = torch.randint(-2**31, 2**31, (4 << n,), dtype=torch.int32, device=dev)
+    b = torch.randint(-2**31, 2**31, (4 << n,), dtype=torch.int32, device=dev)
+    o = torch.empty(4 << n, dtype=torch.int32, device=dev)
+    shat = torch.empty(512, dtype=torch.int32, device=dev)
+    m = g.integers(0, 2**32, size=(128, 4), dtype=np.uint64).astype(np.uint32)
+    ch = g.integers(0, 2**32, size=(n, 4), dtype=np.uint64).astype(np.uint32)
+    ms_copy = [ev_time(lambda: o.copy_(a), reps, st)]
+    ms_pe = ev_time(lambda: B.rs_partial_evals(a, b, n, shat, stream=st), reps, st)
+    ms_map = ev_time(lambda: B.gf128_linear_map(a, o, m, stream=st), reps, st)
+    ms_map_bs = ev_time(lambda: B.gf128_linear_map(o, o, m, bitsliced=True, stream=st), reps, st)
+    ms_mul = ev_time(lambda: B.gf128_mul(a, b, o, stream=st), reps, st)
+    ms_eq = ev_time(lambda: B.eq_expand(n, ch, o, bitsliced=True, stream=st), reps, st)
+    ms_copy.append(ev_time(lambda: o.copy_(a), reps, st))
+    cp = min(ms_copy)
+    out({"config": "rs", "workload": "ring-switching kernels on 2^%d packed GF(2^128) elements" % n,
+         "kernel": "bn::rs_partial_evals, bn::gf128_linear_map", "value": (1 << n) / (ms_pe * 1e-3), "unit": "elements/s (partial evals)",
+         "ms_partial_evals": ms_pe, "ms_linear_map": ms_map, "ms_linear_map_bitsliced_in_place": ms_map_bs, "ms_gf128_mul": ms_mul,
+         "ms_eq_expand_bitsliced": ms_eq, "ms_copy": ms_copy,
+         "partial_evals_over_copy": ms_pe / cp, "linear_map_over_copy": ms_map / cp,
+         "partial_evals_hbm_peak_fraction": (32 << n) / (ms_pe * 1e-3) / HBM_PEAK,
+         # 128 x 128 word pairs per 32-element block, one v_bitop3 lane-operation each: 64 per wave-instruction
+         "partial_evals_bitop3_ceiling_fraction": ((1 << n) / 32 * 16384 / 64) / (ms_pe * 1e-3) / BITOP3_CEILING,
+         "linear_map_hbm_peak_fraction": (32 << n) / (ms_map * 1e-3) / HBM_PEAK, "hbm_peak_bytes_per_s": HBM_PEAK})
+
+
+def rs_pcs_line(dev, out, n=20, log_rate=2, schedule=(4, 4, 4, 4, 4), n_queries=32, runs=3):
+    """Wall time of the packed opening (fri_pcs.prove_eval_packed) of a GF(2) witness of 2^(n+7) bits
+    next to prove_eval of the same committed column in the same process, the best of `runs` each after
+    a warm-up proof, with the splits; verify_eval_packed once."""
+    import torch
+    import binius_ntt_amd as B
+    from binius_ntt_amd import fri_pcs
+    g = np.random.default_rng(19)
+    ntt = B.AdditiveNTT(B.AdditiveNTTConf(n, log_rate, B.FanPaarTowerField(7), device=dev.index or 0))
+    x = torch.randint(-2**31, 2**31, (4 << n,), dtype=torch.int32, device=dev)
+    r = g.integers(0, 2**32, size=(n + 7, 4), dtype=np.uint64).astype(np.uint32)
+    com, state = fri_pcs.commit(ntt, x, list(schedule))
+    torch.cuda.synchronize()
+    best = {}
+    for name, prove in (("packed", lambda: fri_pcs.prove_eval_packed(state, r, n_queries, fri_pcs.Transcript(b"bench"))),
+                        ("plain", lambda: fri_pcs.prove_eval(state, r[7:], n_queries, fri_pcs.Transcript(b"bench")))):
+        for _ in range(runs + 1):
+            t0 = time.perf_counter()
+            proof = prove()
+            torch.cuda.synchronize()
+            s = time.perf_counter() - t0
+            if name not in best or s < best[name][0]:
+                best[name] = (s, dict(state.timing), proof)
+    proof = best["packed"][2]
+    t0 = time.perf_counter()
+    ok = fri_pcs.verify_eval_packed(n + 7, log_rate, list(schedule), com.root, r, proof.v, proof, n_queries, fri_pcs.Transcript(b"bench"))
+    s_verify = time.perf_counter() - t0
+    out({"config": "rs", "workload": "packed FRI-Binius opening, 2^%d bits (n %d), log_rate %d, schedule %s, %d queries"
+         % (n + 7, n, log_rate, "+".join(str(a) for a in schedule), n_queries), "value": best["packed"][0] * 1e3,
+         "unit": "ms per prove_eval_packed (wall)", "ms_split": {k: v * 1e3 for k, v in best["packed"][1].items()},
+         "ms_prove_eval": best["plain"][0] * 1e3, "ms_split_prove_eval": {k: v * 1e3 for k, v in best["plain"][1].items()},
+         "ring_switch_share": best["packed"][1]["ring_switch"] / best["packed"][0], "ms_verify_host": s_verify * 1e3,
          "accepted": bool(ok)})
 
 
@@ -609,6 +685,10 @@ def main():
         bitrev_line(dev, out, 20, False)
     if "pcs" in only:
         pcs_line(dev, out)
+    if "rs" in only:
+        rs_line(dev, out, 24)
+        rs_line(dev, out, 20)
+        rs_pcs_line(dev, out)
     if a.out:
         with open(a.out, "w") as f:
             for d in lines:
